@@ -14,9 +14,22 @@ Multi-GPU: one process per GPU (torchrun); rank r encrypts/decrypts packets
 [r*P, (r+1)*P) of one global synthetic batch (weak scaling, no data-path collective;
 torch.distributed only for the barrier and the max-time reduction).
 
-Also reported: "roofline" for the dominant kernel (algorithmic bytes per launch /
-its mean HIP-event duration vs the 8 TB/s HBM peak) and "cpu_baseline" (the
-reference's own Encryptor compiled into oracle/_ref, timed on this host's cores).
+A plain run sets up, warms up, times the K steps and prints the line: metric, value,
+unit, ms_per_step (wall milliseconds of one timed step) and the description of the job.
+The timed steps are the same in every run (the engine's per-kernel HIP events stay on, as
+in every earlier bench line).
+
+--dump-outputs DIR writes what the last timed step left in the caller's output buffers
+(rank 0's shard) as DIR/cipher.npy and DIR/decrypted.npy, float32 byte values: the whole
+buffer where it is small, else a fixed seeded sample of 1 KiB pieces (dump_outputs).  The
+inputs are synthetic and seeded, so two builds run with the same arguments can be
+compared output for output.
+
+--full adds what the headline does not need: "verify" (round trip, and each rank's
+ciphertext against the reference's digest in tests/golden/digests.json), "roofline" for
+the dominant kernel (algorithmic bytes per launch / its mean HIP-event duration vs the
+8 TB/s HBM peak, and the LDS lookup rate) and "cpu_baseline" (the reference's own
+Encryptor compiled into oracle/_ref, and OpenSSL's, timed on this host's cores).
 """
 from __future__ import annotations
 
@@ -57,10 +70,16 @@ def parse():
     ap.add_argument("--warmup", type=int, default=150)
     ap.add_argument("--packets", type=int, default=W.C2["packets"])
     ap.add_argument("--length", type=int, default=W.C2["length"])
+    ap.add_argument("--full", action="store_true",
+                    help="also verify the outputs against the reference's digests, report the dominant kernel's "
+                         "roofline and time the CPU baselines (a plain run prints the headline figures only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/cipher.npy and DIR/decrypted.npy (float32 byte "
+                         "values; a fixed seeded sample where the buffers are large)")
     ap.add_argument("--cpu-seconds", type=float, default=1.5,
-                    help="target wall time of the multi-thread CPU baseline sample")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-verify", action="store_true")
+                    help="with --full: target wall time of the multi-thread CPU baseline sample")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-verify", action="store_true", help="with --full: skip the output checks")
     ap.add_argument("--pcie", action="store_true", help="also time pinned H2D + kernels + D2H (for DESIGN.md)")
     ap.add_argument("--dist-backend", default="auto",
                     help="auto (RCCL when every local rank has a GPU of its own, else gloo: RCCL refuses two ranks "
@@ -71,7 +90,10 @@ def parse():
                     help="profiling aid: run one direction only (not a bench line)")
     ap.add_argument("--plumbing-only", action="store_true",
                     help="CPU rehearsal of the multi-rank launch/reduction/verify contract (no GPU work)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def _free_port() -> int:
@@ -476,6 +498,37 @@ def alg_bytes_per_launch(nbytes: int, P: int, kw: dict, nkeys: int) -> int:
     return int(2 * nbytes + per_packet * P + 272 * nkeys)
 
 
+DUMP_PIECE = 1024    # bytes per sampled piece (one C2 packet)
+DUMP_PIECES = 4096   # pieces per array: 4 Mi values = 16 MiB of float32, two arrays per run
+DUMP_SEED = 20260
+
+
+def dump_sample_index(nbytes: int):
+    """Byte positions written for a buffer of nbytes: None (all of it) up to DUMP_PIECES
+    pieces, else the first and last piece and a seeded choice of the others, ascending."""
+    npieces = nbytes // DUMP_PIECE
+    if npieces <= DUMP_PIECES:
+        return None
+    rng = np.random.default_rng(DUMP_SEED)
+    pick = rng.choice(npieces - 2, DUMP_PIECES - 2, replace=False) + 1
+    pieces = np.sort(np.concatenate([[0, npieces - 1], pick])).astype(np.int64)
+    return (pieces[:, None] * DUMP_PIECE + np.arange(DUMP_PIECE, dtype=np.int64)[None, :]).reshape(-1)
+
+
+def dump_outputs(path: str, outputs: dict) -> dict:
+    """Write each output buffer (uint8, on the device) as path/<name>.npy in float32; the
+    same positions of every buffer, from dump_sample_index.  Returns what was written."""
+    os.makedirs(path, exist_ok=True)
+    written = {}
+    for name, buf in outputs.items():
+        idx = dump_sample_index(buf.numel())
+        part = buf if idx is None else buf.index_select(0, torch.from_numpy(idx).to(buf.device))
+        arr = part.cpu().numpy().astype(np.float32)
+        np.save(os.path.join(path, name + ".npy"), arr)
+        written[name] = {"values": int(arr.size), "of": int(buf.numel()), "sampled": idx is not None}
+    return written
+
+
 def plumbing_only(args, world, rank):
     """CPU rehearsal of the multi-rank contract (tests/test_bench_launcher.py): the
     launcher's world/rank environment, the barrier, max-over-ranks time and the
@@ -545,10 +598,59 @@ def main():
     eng.set_timing(False)
     dev = "cuda" if args.dist_backend == "nccl" else None
     elapsed = max_over_ranks(elapsed, world, dev)
+    total_bytes = sum_over_ranks(nbytes, world, dev)
+
+    directions = 2 if args.only is None else 1
+    payload = float(directions) * total_bytes * args.steps
+    value = payload / elapsed / 2**30
+
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        outputs = {}
+        if args.only != "decrypt":
+            outputs["cipher"] = cipher
+        if args.only != "encrypt":
+            outputs["decrypted"] = back
+        dumped = dump_outputs(args.dump_outputs, outputs)
+
+    line = {
+        "metric": METRIC,
+        "value": round(value, 3),
+        "unit": "GiB/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+        "higher_is_better": True,
+        "scaling": job["scaling"],
+        "vs_baseline": None,
+        "dtype": "u8",
+        "data": job["data"],
+        "config": job["config"],
+        "full": args.full,
+    }
+    if dumped is not None:
+        line["dumped_outputs"] = dumped
+    if args.full:
+        line.update(full_report(args, eng, job, cipher, back, world, rank, local))
+    if args.pcie and rank == 0 and job["uniform"]:
+        line["pcie_inclusive"] = pcie_rate(eng, ks, P, job["L"])
+    if rank == 0:
+        print(json.dumps(line), flush=True)
+    if world > 1:
+        import torch.distributed as dist
+        dist.destroy_process_group()
+
+
+def full_report(args, eng, job, cipher, back, world, rank, local) -> dict:
+    """What --full adds to the line: "verify", "roofline" (from the HIP events of the timed
+    steps) and "cpu_baseline" (every rank calls it: the verify gather is a collective)."""
+    import fpnn_amd
+    plain, ks, kw, P = job["plain"], job["ks"], job["kw"], job["P"]
+    nbytes = plain.numel()
     n_enc, ms_enc = eng.kernel_stats(fpnn_amd.K_ENCRYPT)
     n_dec, ms_dec = eng.kernel_stats(fpnn_amd.K_DECRYPT)
     names = (eng.last_kernel(fpnn_amd.K_ENCRYPT), eng.last_kernel(fpnn_amd.K_DECRYPT))
-    total_bytes = sum_over_ranks(nbytes, world, dev)
 
     verify = None
     if not args.no_verify:
@@ -557,10 +659,6 @@ def main():
                                 for r in ranks),
                   "every_rank_checked_against_reference": all("cipher_sha256_matches_reference" in r for r in ranks),
                   "ranks": ranks}
-
-    directions = 2 if args.only is None else 1
-    payload = float(directions) * total_bytes * args.steps
-    value = payload / elapsed / 2**30
 
     # roofline for the dominant kernel: algorithmic bytes per launch
     alg_bytes = alg_bytes_per_launch(nbytes, P, kw, job["nkeys"])
@@ -595,34 +693,7 @@ def main():
         host_plain = plain.cpu().numpy()
         cpu = cpu_baseline(host_plain, P, job["L"], job["key"], job["iv"], args.cpu_seconds, cipher.cpu().numpy())
 
-    extra = {}
-    if args.pcie and rank == 0 and job["uniform"]:
-        extra["pcie_inclusive"] = pcie_rate(eng, ks, P, job["L"])
-
-    if rank == 0:
-        line = {
-            "metric": METRIC,
-            "value": round(value, 3),
-            "unit": "GiB/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-            "higher_is_better": True,
-            "scaling": job["scaling"],
-            "vs_baseline": None,
-            "dtype": "u8",
-            "data": job["data"],
-            "config": job["config"],
-            "roofline": roofline,
-            "cpu_baseline": cpu,
-            "verify": verify,
-        }
-        line.update(extra)
-        print(json.dumps(line), flush=True)
-    if world > 1:
-        import torch.distributed as dist
-        dist.destroy_process_group()
+    return {"roofline": roofline, "cpu_baseline": cpu, "verify": verify}
 
 
 if __name__ == "__main__":

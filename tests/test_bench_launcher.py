@@ -77,6 +77,37 @@ def test_shard_digests_cover_every_rank():
     assert shards["C5/w1/r0"] == d["C5"]["cipher_sha256"]
 
 
+def test_dump_outputs_sample_is_fixed_and_bounded(tmp_path):
+    """--dump-outputs: small buffers whole, large ones as the same seeded 1 KiB pieces on
+    every run (first and last piece included), float32, two C2-sized arrays within 64 MB."""
+    import numpy as np
+    import torch
+    import bench
+    assert bench.dump_sample_index(bench.DUMP_PIECES * bench.DUMP_PIECE) is None
+    n = 1 << 30  # one C2 buffer
+    idx = bench.dump_sample_index(n)
+    assert np.array_equal(idx, bench.dump_sample_index(n))
+    assert idx.size == bench.DUMP_PIECES * bench.DUMP_PIECE and 2 * 4 * idx.size + 256 <= 64_000_000
+    assert idx[0] == 0 and idx[-1] == n - 1 and np.all(np.diff(idx) > 0)
+    assert np.all(np.diff(idx.reshape(-1, bench.DUMP_PIECE), axis=1) == 1)  # whole pieces
+    m = (bench.DUMP_PIECES + 3) * bench.DUMP_PIECE + 5
+    big = torch.from_numpy((np.arange(m) % 251).astype(np.uint8))
+    small = big[:3000]
+    info = bench.dump_outputs(str(tmp_path / "d"), {"cipher": big, "decrypted": small})
+    a, b = np.load(tmp_path / "d" / "cipher.npy"), np.load(tmp_path / "d" / "decrypted.npy")
+    assert a.dtype == np.float32 and b.dtype == np.float32
+    assert np.array_equal(a, big.numpy()[bench.dump_sample_index(m)].astype(np.float32))
+    assert np.array_equal(b, small.numpy().astype(np.float32))
+    assert info["cipher"] == {"values": a.size, "of": m, "sampled": True}
+    assert info["decrypted"] == {"values": 3000, "of": 3000, "sampled": False}
+
+
+def test_steps_must_be_positive():
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "0"],
+                         env=_env_without_dist(), capture_output=True, text=True, timeout=120, cwd=ROOT)
+    assert out.returncode == 2 and "--steps" in out.stderr
+
+
 def test_cpu_baseline_leg_runs_on_cpu():
     """bench.cpu_baseline end to end on a small sample (the leg the GPU bench runs on rank 0):
     every field of the JSON object is produced and the CPU output is checked against the

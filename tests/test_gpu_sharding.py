@@ -32,7 +32,7 @@ def _env():
 @pytest.mark.parametrize("workload,world", [("C4", 2), ("C5", 2), ("C4", 4), ("C5", 4), ("C4", 8), ("C5", 8)])
 def test_sharded_config_every_rank_matches_reference(workload, world):
     cmd = [sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--workload", workload,
-           "--dist-backend", "gloo", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+           "--dist-backend", "gloo", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"]
     out = subprocess.run(cmd, env=_env(), capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]

@@ -14,7 +14,7 @@
 #   guard            tests/cpp/guard_pages.cpp: ragged encrypts over arrays abutting unmapped pages
 #   guard_audit      the same through the address-audit build (libfpnn_aes_gpu_audit.so)
 #   audit:<expr>     pytest -m gpu -k <expr> through the address-audit build
-#   bench            python bench.py (the contract line)
+#   bench            python bench.py --full (the contract line with verify, roofline and CPU baselines)
 #   bench_driver     bench.py three times with the driver's arguments (--steps 20 --warmup 5)
 #   bench_trace      bench.py under rocprofv3 --kernel-trace --stats (profiles the line's kernels)
 #   bench_pmc        bench.py under the five PMC passes (HBM bytes, LDS, VALU, waits, EA read sizes)
@@ -91,7 +91,7 @@ for step in "$@"; do
       else FPNN_AES_GPU_LIB=$PWD/fpnn_amd/libfpnn_aes_gpu_audit.so run "$glog" 300 "$OUT/guard_pages" ${gargs//,/ }; fi ;;
     audit:*) FPNN_AES_GPU_LIB=$PWD/fpnn_amd/libfpnn_aes_gpu_audit.so run audit 900 python -u -m pytest tests -q -m gpu \
         --timeout 300 --timeout-method thread -p no:cacheprovider -k "${step#audit:}" ;;
-    bench) run bench 300 python -u bench.py ;;
+    bench) run bench 300 python -u bench.py --full ;;
     bench_driver) for i in 1 2 3; do  # the driver's own arguments (BENCH_rNN.json: --steps 20 --warmup 5)
         run "bench_driver_$i" 300 python -u bench.py --gpus 1 --steps 20 --warmup 5
       done ;;

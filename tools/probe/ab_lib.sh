@@ -9,7 +9,7 @@ for i in 1 2; do
   for v in ${3:-base new}; do
     lib=$PWD/fpnn_amd/libfpnn_aes_gpu.so; [ $v != new ] && lib=$PWD/fpnn_amd/libfpnn_aes_gpu_$v.so
     if [ "$2" = bench ]; then
-      FPNN_AES_GPU_LIB=$lib timeout -k 10 300 python -u bench.py --no-cpu-baseline > "$OUT/ab_${v}_$i.log" 2>&1 || exit 3
+      FPNN_AES_GPU_LIB=$lib timeout -k 10 300 python -u bench.py --full --no-cpu-baseline > "$OUT/ab_${v}_$i.log" 2>&1 || exit 3
       echo "$v #$i: $(grep -o '"value": [0-9.]*\|"payload_GiBs": [0-9.]*' "$OUT/ab_${v}_$i.log" | tr '\n' ' ')"
     else
       FPNN_AES_GPU_LIB=$lib timeout -k 10 300 python -u tools/bench_configs.py --reps 3 --no-host --configs "$2" \
