@@ -11,12 +11,15 @@
 //
 // stdin, one request per line (hex without spaces):
 //   S <curve> <server_private> <peer_public> <keylen>   ECCKeyExchange::init + calcKey
-//       -> "R <init_ok> <calc_ok> <key> <iv>"   (FPLog writes its records to stdout too)
+//       -> "R <init_ok> <calc_ok> <key> <iv>"
 //   T <curve> <server_private> <peer_public> <reps>     time `reps` calcKey calls (CPU baseline)
 //       -> "R <seconds> <calc_ok>"
 //   C <curve> <rng_bytes> <server_public> <keylen>      ECCKeysMaker: setCurve, publicKey
 //       (private key drawn from rng_bytes), setPeerPublicKey, calcKey
 //       -> "R <public> <private> <calc_ok> <key> <iv>"
+// Answers go to the stdout the harness was started with; FPLog also writes its records to
+// file descriptor 1 (from its own thread, so that a record could land inside an answer line
+// and lose it), which main() therefore points at stderr before the first request.
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
@@ -34,6 +37,7 @@ using namespace fpnn;
 
 namespace {
 
+FILE *g_res = nullptr;  // the answers ("R ..." lines): the original stdout
 std::vector<uint8_t> g_queue;
 uint64_t g_state = 0x9E3779B97F4A7C15ull;
 
@@ -76,6 +80,9 @@ struct MakerProbe : ECCKeysMaker {
 }  // namespace
 
 int main() {
+    fflush(stdout);
+    g_res = fdopen(dup(STDOUT_FILENO), "w");
+    if (!g_res || dup2(STDERR_FILENO, STDOUT_FILENO) < 0) return 3;
     Setting::set("FP.server.local.ip4", "127.0.0.1");  // see framing_ref.cpp
     uECC_set_rng(&harness_rng);
     std::string op, curve, a, b;
@@ -86,7 +93,7 @@ int main() {
             ECCKeyExchange ex;
             const bool init_ok = ex.init(curve, unhex(a));
             const bool ok = init_ok && ex.calcKey(key, iv, keylen, unhex(b));
-            printf("R %d %d %s %s\n", init_ok ? 1 : 0, ok ? 1 : 0, hex(key, ok ? keylen : 0).c_str(),
+            fprintf(g_res, "R %d %d %s %s\n", init_ok ? 1 : 0, ok ? 1 : 0, hex(key, ok ? keylen : 0).c_str(),
                    hex(iv, ok ? 16 : 0).c_str());
         } else if (op == "T") {
             ECCKeyExchange ex;
@@ -96,13 +103,13 @@ int main() {
             bool ok = true;
             for (int r = 0; r < keylen; r++) ok = ex.calcKey(key, iv, 32, peer) && ok;
             const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-            printf("R %.6f %d\n", dt, ok ? 1 : 0);
+            fprintf(g_res, "R %.6f %d\n", dt, ok ? 1 : 0);
         } else if (op == "C") {
             const std::string q = unhex(a);
             g_queue.assign(q.begin(), q.end());
             MakerProbe m;
             if (!m.setCurve(curve)) {
-                printf("R - - 0 - -\n");
+                fprintf(g_res, "R - - 0 - -\n");
                 continue;
             }
             const std::string pub = m.publicKey();
@@ -110,14 +117,14 @@ int main() {
             m.setPeerPublicKey(unhex(b));
             const bool ok = m.calcKey(key, iv, keylen);
             const std::string &priv = m.privateKey();
-            printf("R %s %s %d %s %s\n", hex((const uint8_t *)pub.data(), pub.size()).c_str(),
+            fprintf(g_res, "R %s %s %d %s %s\n", hex((const uint8_t *)pub.data(), pub.size()).c_str(),
                    hex((const uint8_t *)priv.data(), priv.size()).c_str(), ok ? 1 : 0,
                    hex(key, ok ? keylen : 0).c_str(), hex(iv, ok ? 16 : 0).c_str());
         } else {
             return 2;
         }
-        fflush(stdout);
+        fflush(g_res);
     }
-    fflush(stdout);
+    fflush(g_res);
     _exit(0);
 }

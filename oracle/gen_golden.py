@@ -12,6 +12,9 @@ container only).  Writes data only -- inputs and the reference's outputs:
   modes_cases.json  the rest of rijndael.h: setup_decrypt, ECB decrypt, CBC, OFB
   framing_cases.json wire streams through the reference's EncryptedPackageReceiver /
                     EncryptedStreamReceiver (oracle/_ref/framing_ref): frames, plaintexts, verdicts
+  ecdh_edge_cases.json  ECCKeyExchange::calcKey on edge scalars (0, 1, n - 1, n, n + 1, 2^bits - 1, ...)
+                    and edge peers (coordinates 0, 1, p - 1, p, p + 1, 2^bits - 1, ...; on-curve
+                    points with tiny or near-p x; x or y not reduced), S requests only
   ecdh_cases.json   ECCKeyExchange / ECCKeysMaker (core/KeyExchange.cpp + micro-ecc) on the
                     four curves (oracle/_ref/ecdh_ref): public keys, derived keys and IVs
   digests.json      SHA-256 digests of full-size synthetic config batches (C2, C3, C5) and
@@ -467,6 +470,93 @@ def gen_ecdh_cases():
     return out
 
 
+def _sqrt_mod(a, p):
+    """A square root of a mod the prime p (Tonelli-Shanks), or None."""
+    a %= p
+    if a == 0:
+        return 0
+    if pow(a, (p - 1) // 2, p) != 1:
+        return None
+    q, s = p - 1, 0
+    while q % 2 == 0:
+        q, s = q // 2, s + 1
+    z = 2
+    while pow(z, (p - 1) // 2, p) != p - 1:
+        z += 1
+    m, c, t, r = s, pow(z, q, p), pow(a, q, p), pow(a, (q + 1) // 2, p)
+    while t != 1:
+        i, t2 = 0, t
+        while t2 != 1:
+            t2, i = t2 * t2 % p, i + 1
+        b = pow(c, 1 << (m - i - 1), p)
+        m, c, t, r = i, b * b % p, t * b * b % p, r * b % p
+    return r
+
+
+def ecdh_edge_requests(c):
+    """The (private, peer x, peer y) integers of one curve's edge cases: every edge scalar, every
+    edge coordinate value in the x and in the y position, on-curve points with tiny or near-p x
+    (and their negatives), and such a point with x + p (not reduced)."""
+    p, n, bits = c.p, c.n, 8 * c.num_bytes
+    top = 1 << bits
+    assert bits == 8 * c.private_bytes
+    scalars = [0, 1, 2, 3, n - 2, n - 1, n, n + 1, (n - 1) // 2, (n + 1) // 2, top - 1, top >> 1, top - n]
+    coords = [0, 1, 2, p - 2, p - 1, p, p + 1, top - 1, top >> 1, (1 << 96) - 1]
+    a = -3 if c.a_minus3 else 0
+
+    def on_curve(xs):
+        for x in xs:
+            y = _sqrt_mod(x * x * x + a * x + c.b, p)
+            if y:
+                return [(x, y), (x, p - y)]
+        raise AssertionError("no point found")
+
+    tiny, near_p = on_curve(range(1, 64)), on_curve(range(p - 1, p - 64, -1))
+    pts = tiny + near_p
+    pts.append(next((x + p, y) for x, y in tiny if x + p < top))      # x not reduced
+    # (y + p < 2^bits needs y < 2^bits - p, 2^32 .. 2^224: no such point among these; the y
+    # values p and p + 1 of the coordinate grid below are the not-reduced y inputs)
+    reqs = []
+    grid = [(coords[i], coords[(i + j) % len(coords)]) for j in (0, 3, 7) for i in range(len(coords))]
+    for i, peer in enumerate(grid):                                    # every coordinate value in x and in y
+        reqs.append((scalars[i % len(scalars)],) + peer)
+    for k in scalars:                                                  # every scalar on real points
+        reqs += [(k,) + pt for pt in pts]
+    for k in (2, n - 2, (n - 1) // 2, top - 1):                        # a full ladder on degenerate peers
+        reqs += [(k,) + grid[i] for i in range(0, len(grid), 3)]
+    assert {r[0] for r in reqs} == set(scalars)
+    assert {r[1] for r in reqs} >= set(coords) and {r[2] for r in reqs} >= set(coords)
+    return reqs
+
+
+def gen_ecdh_edge_cases():
+    """ECCKeyExchange::init + calcKey (oracle/_ref/ecdh_ref, S requests only) on edge scalars
+    and peers of the four curves -> tests/golden/ecdh_edge_cases.json; key lengths 16 and 32
+    alternate.  Requests go in batches of 100 and every batch's answer count is checked."""
+    import subprocess
+    from ecdh_oracle import CURVES
+    out = {"source": "oracle/_ref/ecdh_ref: the reference's core/KeyExchange.cpp + core/micro-ecc/uECC.c "
+                     "(ECCKeyExchange::init + calcKey)", "curves": []}
+    for name, c in CURVES.items():
+        nb, pb = c.num_bytes, c.private_bytes
+        rows = [{"private": k.to_bytes(pb, "big").hex(), "peer": (x.to_bytes(nb, "big") + y.to_bytes(nb, "big")).hex(),
+                 "keylen": (16, 32)[i % 2]} for i, (k, x, y) in enumerate(ecdh_edge_requests(c))]
+        for at in range(0, len(rows), 100):
+            batch = rows[at:at + 100]
+            r = subprocess.run([ECDH_REF], input="".join(f"S {name} {s['private']} {s['peer']} {s['keylen']}\n"
+                                                         for s in batch),
+                               capture_output=True, text=True, timeout=300)
+            assert r.returncode == 0, (r.returncode, r.stderr[-2000:])
+            res = [ln.split() for ln in r.stdout.splitlines() if ln.startswith("R ")]
+            assert len(res) == len(batch), (name, at, len(res), len(batch))
+            for s, (_, init_ok, ok, key, iv) in zip(batch, res):
+                assert init_ok == "1", (name, s)
+                s.update(ok=int(ok), key="" if key == "-" else key, iv="" if iv == "-" else iv)
+        out["curves"].append({"curve": name, "server": rows})
+        print(f"  ecdh edge {name}: {len(rows)} calls, {sum(s['ok'] for s in rows)} ok")
+    return out
+
+
 def ref_buf(b):
     import ctypes as C
     return C.cast(C.c_char_p(b), C.POINTER(C.c_uint8))
@@ -589,6 +679,7 @@ def main():
     ap.add_argument("--modes-only", action="store_true", help="only (re)write modes_cases.json")
     ap.add_argument("--framing-only", action="store_true", help="only (re)write framing_cases.json")
     ap.add_argument("--ecdh-only", action="store_true", help="only (re)write ecdh_cases.json")
+    ap.add_argument("--ecdh-edge-only", action="store_true", help="only (re)write ecdh_edge_cases.json")
     ap.add_argument("--c1-only", action="store_true", help="only (re)write c1_cases.json")
     ap.add_argument("--multi-only", action="store_true", help="only (re)write multi_cases.json")
     ap.add_argument("--udp-only", action="store_true", help="only (re)write udp_cases.json")
@@ -610,6 +701,9 @@ def main():
         return
     if args.ecdh_only:
         dump("ecdh_cases.json", gen_ecdh_cases())
+        return
+    if args.ecdh_edge_only:
+        dump("ecdh_edge_cases.json", gen_ecdh_edge_cases())
         return
     if args.c1_only:
         dump("c1_cases.json", gen_c1_cases())
@@ -633,6 +727,7 @@ def main():
     dump("modes_cases.json", gen_modes_cases(ref))
     dump("framing_cases.json", gen_framing_cases(ref))
     dump("ecdh_cases.json", gen_ecdh_cases())
+    dump("ecdh_edge_cases.json", gen_ecdh_edge_cases())
     dump("c1_cases.json", gen_c1_cases())
     dump("multi_cases.json", gen_multi_cases())
     dump("udp_cases.json", gen_udp_cases())

@@ -1,4 +1,4 @@
-"""The special-prime reductions and inversion chains of k_ecdh.hip (field kinds FK_K1,
+"""The special-prime reductions and inversion chains of ecc_field.hpp (field kinds FK_K1,
 FK_P256, FK_P224, FK_P192), restated limb for limb in Python and checked against plain
 modular arithmetic -- including the carry-range assumptions the device code relies on
 (column sums < 2^64, final carries in {-1, 0, 1} or {0, 1}, values < 2p before the last
@@ -27,10 +27,13 @@ def value(u):
     return sum(w << (32 * i) for i, w in enumerate(u))
 
 
-def settle(u, cr, p, nw):
-    """value = U + cr * 2^(32 nw), cr in {-1, 0, 1} -> [0, p) (p256_fold / p224_fold tail)."""
+def settle(u, cr, p, nw, k=None, rec=None):
+    """value = U + cr * 2^(32 nw), cr in {-1, 0, 1} -> [0, p) (p256_fold / p224_fold tail).
+    rec (a list): gets the branch tuple (k, cr, U >= p)."""
     assert cr in (-1, 0, 1)
     U, top = value(u), 1 << (32 * nw)
+    if rec is not None:
+        rec.append((k, cr, U >= p))
     if cr < 0:
         return (U + p) % top
     if cr > 0 or U >= p:
@@ -38,7 +41,8 @@ def settle(u, cr, p, nw):
     return U
 
 
-def k1_fold(t):  # k_ecdh.hip k1_fold: three carry chains, a top fold, one subtraction
+def k1_fold(t, rec=None):  # ecc_field.hpp k1_fold: three carry chains, a top fold, one subtraction
+    # rec (a list): gets the branch tuple (u9, cy, v >= p)
     p = P["secp256k1"]
 
     def addc(x, y, c):
@@ -73,10 +77,12 @@ def k1_fold(t):  # k_ecdh.hip k1_fold: three carry chains, a top fold, one subtr
         u[i], cy = addc(u[i], 0, cy)
     v = value(u) + (cy << 256)
     assert v < 2 * p
+    if rec is not None:
+        rec.append((u9, cy, v >= p))
     return v - p if v >= p else v
 
 
-def p256_fold(t):  # k_ecdh.hip p256_fold: nine 8-limb chains, a signed top, one fold, settle
+def p256_fold(t, rec=None):  # ecc_field.hpp p256_fold: nine 8-limb chains, a signed top, one fold, settle
     W = 1 << 256
 
     def add(x, y):  # add_n<8>: (sum mod 2^256, carry)
@@ -111,10 +117,10 @@ def p256_fold(t):  # k_ecdh.hip p256_fold: nine 8-limb chains, a signed top, one
     kp, kn = max(k, 0), max(-k, 0)
     u, ca = add(u, [kp, 0, 0, kn, 0, 0, kn, kp])
     u, cb = sub(u, [kn, 0, 0, kp, 0, 0, kp, kn])
-    return settle(u, ca - cb, P["secp256r1"], 8)
+    return settle(u, ca - cb, P["secp256r1"], 8, k, rec)
 
 
-def p224_fold(t):  # k_ecdh.hip p224_fold: four 7-limb chains, a signed top, one fold, settle
+def p224_fold(t, rec=None):  # ecc_field.hpp p224_fold: four 7-limb chains, a signed top, one fold, settle
     W = 1 << 224
 
     def add(x, y):
@@ -137,10 +143,11 @@ def p224_fold(t):  # k_ecdh.hip p224_fold: four 7-limb chains, a signed top, one
     kp, kn = max(k, 0), max(-k, 0)
     u, ca = add(u, [kn, 0, 0, kp, 0, 0, 0])
     u, cb = sub(u, [kp, 0, 0, kn, 0, 0, 0])
-    return settle(u, ca - cb, P["secp224r1"], 7)
+    return settle(u, ca - cb, P["secp224r1"], 7, k, rec)
 
 
-def p192_fold(t):  # k_ecdh.hip p192_fold: three 6-limb chains, one fold chain, one subtraction
+def p192_fold(t, rec=None):  # ecc_field.hpp p192_fold: three 6-limb chains, one fold chain, one subtraction
+    # rec (a list): gets the branch tuple (k, cy, v >= p)
     W = 1 << 192
 
     def add(x, y):
@@ -158,6 +165,8 @@ def p192_fold(t):  # k_ecdh.hip p192_fold: three 6-limb chains, one fold chain, 
     p = P["secp192r1"]
     v = value(u) + (cy << 192)
     assert v < 2 * p
+    if rec is not None:
+        rec.append((k, cy, v >= p))
     return v - p if v >= p else v
 
 
@@ -201,13 +210,129 @@ def test_fold_matches_mod(curve):
             assert fold(ws) == value(ws) % p
 
 
+# Branch values the shared vector set (tests/ecc_vectors.py) must take in each fold: what
+# tests/test_gpu_ecc_field.py runs through the compiled device code.  A floor: the set may
+# reach more.  Per curve: {field of the fold's branch tuple: values}, for the products a * b
+# (a, b < p) and for products and raw words t < p^2 together.
+#   k1_fold   (u9, cy, v >= p)      p192_fold (k, cy, v >= p)
+#   p256_fold / p224_fold (k, cr, U >= p)   [U >= p decides only where cr == 0]
+# These are all the values that a product's word t <= (p - 1)^2 can give: test_fold_top_word_range
+# below proves that secp256k1's u9 = 2, secp256r1's k = 5, 6, secp224r1's k = -2, 2 and cr != 0 and
+# secp192r1's k = 3 cannot occur there (the restatements' range assertions -4 <= k <= 6 etc. are
+# the design's bounds for any 2*NW-limb input).
+REACHED = {
+    "secp256k1": {"products": ({0, 1}, {0, 1}, {False, True}), "all": ({0, 1}, {0, 1}, {False, True})},
+    "secp256r1": {"products": (set(range(-4, 4)), {-1, 0, 1}, {False, True}),
+                  "all": (set(range(-4, 5)), {-1, 0, 1}, {False, True})},
+    "secp224r1": {"products": ({-1, 0, 1}, {0}, {False, True}), "all": ({-1, 0, 1}, {0}, {False, True})},
+    "secp192r1": {"products": ({0, 1, 2}, {0, 1}, {False, True}), "all": ({0, 1, 2}, {0, 1}, {False, True})},
+}
+
+
+@pytest.mark.parametrize("curve", sorted(P))
+def test_vectors_reach_fold_branches(curve):
+    """The operand pairs and raw words of tests/ecc_vectors.py fold correctly here and take
+    every branch value of REACHED -- the rare ones (a final carry, a settle with cr = +-1, a
+    result in [p, 2^bits)) that random operands meet with a chance of 2^-32 .. 2^-189."""
+    import ecc_vectors as V
+    p, nw, fold = P[curve], NW[curve], FOLD[curve]
+    assert (V.P[curve], V.NW[curve]) == (p, nw)
+    rec = []
+    for a, b in V.product_pairs(curve):
+        assert 0 <= a < p and 0 <= b < p
+        assert fold(limbs(a * b, 2 * nw), rec) == a * b % p
+    prod = set(rec)
+    del rec[:]
+    for ws in V.raw_words(curve):
+        assert len(ws) == 2 * nw and value(ws) < p * p
+        assert fold(list(ws), rec) == value(ws) % p
+    both = prod | set(rec)
+    for name, seen in (("products", prod), ("all", both)):
+        for i, want in enumerate(REACHED[curve][name]):
+            got = {t[i] for t in seen}
+            assert want <= got, (curve, name, i, sorted(want - got, key=str))
+    if curve in ("secp256r1", "secp224r1"):  # U >= p matters where cr == 0: both ways there
+        assert {t[2] for t in prod if t[1] == 0} == {False, True}
+
+
+# FIPS 186-4 D.2 word sums, independent of the restatements above: (multiplier, limb of t at each
+# position; None = 0).  S(t) = sum of multiplier * word is linear in t's limbs, S = t (mod p), and a
+# fold's top word k is floor(S / 2^(32 NW)).
+_N = None
+WORDSUM = {
+    "secp256r1": [(1, [0, 1, 2, 3, 4, 5, 6, 7]), (2, [_N, _N, _N, 11, 12, 13, 14, 15]),
+                  (2, [_N, _N, _N, 12, 13, 14, 15, _N]), (1, [8, 9, 10, _N, _N, _N, 14, 15]),
+                  (1, [9, 10, 11, 13, 14, 15, 13, 8]), (-1, [11, 12, 13, _N, _N, _N, 8, 10]),
+                  (-1, [12, 13, 14, 15, _N, _N, 9, 11]), (-1, [13, 14, 15, 8, 9, 10, _N, 12]),
+                  (-1, [14, 15, _N, 9, 10, 11, _N, 13])],
+    "secp224r1": [(1, [0, 1, 2, 3, 4, 5, 6]), (1, [_N, _N, _N, 7, 8, 9, 10]), (1, [_N, _N, _N, 11, 12, 13, _N]),
+                  (-1, [7, 8, 9, 10, 11, 12, 13]), (-1, [11, 12, 13, _N, _N, _N, _N])],
+    "secp192r1": [(1, [0, 1, 2, 3, 4, 5]), (1, [6, 7, 6, 7, _N, _N]), (1, [_N, _N, 8, 9, 8, 9]),
+                  (1, [10, 11, 10, 11, 10, 11])],
+}
+
+
+def _wordsum_weights(curve):
+    w = [0] * (2 * NW[curve])
+    for mult, idx in WORDSUM[curve]:
+        for pos, i in enumerate(idx):
+            if i is not None:
+                w[i] += mult << (32 * pos)
+    return w
+
+
+def _extreme_word(w, bound):
+    """The limbs t, 0 <= t <= bound (as integers), that maximise sum(t[i] * w[i]) -- exactly: t is
+    `bound`, or equals it above some limb j, is smaller at j and free below, and the sum is
+    separable, so the best word of each such shape is known."""
+    cands = [list(bound)]
+    for j in range(len(bound)):
+        if bound[j] > 0:
+            below = [M - 1 if w[i] > 0 else 0 for i in range(j)]
+            cands.append(below + [bound[j] - 1 if w[j] > 0 else 0] + bound[j + 1:])
+    return max(cands, key=lambda t: sum(x * y for x, y in zip(t, w)))
+
+
+def test_fold_top_word_range():
+    """The exact range of every fold's top word over the words a product can give, t <= (p - 1)^2:
+    secp256r1 k in [-4, 4], secp224r1 k in [-1, 1] with a settle carry cr = 0, secp192r1 k in
+    [0, 2], secp256k1 u9 <= 1 -- so the values REACHED lists are all there are."""
+    import ecc_vectors as V
+    want = {"secp256r1": (-4, 4), "secp224r1": (-1, 1), "secp192r1": (0, 2)}
+    for curve, (kmin, kmax) in want.items():
+        p, nw, fold = P[curve], NW[curve], FOLD[curve]
+        W = 1 << (32 * nw)
+        w = _wordsum_weights(curve)
+
+        def S(t):
+            return sum(x * y for x, y in zip(t, w))
+        for ws in V.raw_words(curve)[:400]:  # the table is the restatement's sum: S = t (mod p), k = floor(S / W)
+            rec = []
+            fold(list(ws), rec)
+            assert S(ws) % p == value(ws) % p and S(ws) // W == rec[0][0]
+        bound = limbs((p - 1) ** 2, 2 * nw)
+        hi, lo = _extreme_word(w, bound), _extreme_word([-x for x in w], bound)
+        assert value(hi) <= (p - 1) ** 2 and value(lo) <= (p - 1) ** 2
+        assert (S(lo) // W, S(hi) // W) == (kmin, kmax), curve
+        for t, k in ((hi, kmax), (lo, kmin)):  # and the extremes are reached
+            rec = []
+            assert fold(t, rec) == value(t) % p and rec[0][0] == k
+        if curve == "secp224r1":
+            # the fold adds k (2^96 - 1) to U = S mod W: a carry needs S >= 2W - 2^96 + 1, a borrow
+            # S < -W + 2^96 - 1
+            assert S(hi) < 2 * W - (1 << 96) + 1 and S(lo) >= -W + (1 << 96) - 1
+    # secp256k1: u8 + u9 2^32 = floor((L + H (2^32 + 977)) / 2^256) with L, H < 2^256
+    top = 1 << 256
+    assert ((top - 1) + (top - 1) * ((1 << 32) + 977)) >> 256 < 2 << 32
+
+
 def _sq(x, n, p):
     for _ in range(n):
         x = x * x % p
     return x
 
 
-def inv_chain(curve, a):  # k_ecdh.hip finv, special forms
+def inv_chain(curve, a):  # ecc_field.hpp finv, special forms
     p = P[curve]
 
     def blk(x, n, y):

@@ -88,6 +88,7 @@ def test_random_peers_vs_oracle(engine, curve):
     n = 96
     privs = [int.from_bytes(rng.bytes(c.private_bytes), "big") % c.n for _ in range(n)]
     privs[:4] = [1, c.n - 1, c.n - 2, 2]
+    privs[7:10] = [c.n, c.n + 5, (1 << (8 * c.private_bytes)) - 1]  # not reduced: the per-lane k + n / k + 2n select
     pb = b"".join(k.to_bytes(c.private_bytes, "big") for k in privs)
     pub, ok = engine.ecdh_public_keys(curve, _dev(pb))
     torch.cuda.synchronize()

@@ -260,6 +260,35 @@ def test_ecdh_restatement_vs_reference():
     assert fails >= 4 * 5  # zero point, short peer, bad keylen, private 1, short private per curve
 
 
+def test_ecdh_restatement_vs_reference_edge_cases():
+    """oracle/ecdh_oracle.py against the reference on edge scalars and peers
+    (tests/golden/ecdh_edge_cases.json, written by oracle/_ref/ecdh_ref): scalars 0, 1, 2, 3,
+    n - 2 .. n + 1, (n +- 1) / 2, 2^bits - 1, 2^(bits - 1), 2^bits - n; peer coordinates 0, 1, 2,
+    p - 2 .. p + 1, 2^bits - 1, 2^(bits - 1), 2^96 - 1 in both positions; on-curve points with
+    tiny or near-p x, their negatives, and x not reduced.  Every row, failures included."""
+    sys.path.insert(0, os.path.join(ROOT, "oracle"))
+    import ecdh_oracle as E
+    with open(os.path.join(ROOT, "tests", "golden", "ecdh_edge_cases.json")) as f:
+        g = json.load(f)
+    assert {c["curve"] for c in g["curves"]} == set(E.CURVES)
+    for cv in g["curves"]:
+        c = E.CURVES[cv["curve"]]
+        p, n, top = c.p, c.n, 1 << (8 * c.num_bytes)
+        assert len(cv["server"]) >= 100
+        for s in cv["server"]:
+            ok, key, iv = E.calc_key(cv["curve"], bytes.fromhex(s["private"]), bytes.fromhex(s["peer"]), s["keylen"])
+            assert (int(ok), key.hex(), iv.hex()) == (s["ok"], s["key"], s["iv"]), (cv["curve"], s)
+        # the fixture holds what it is meant to hold
+        scalars = {int(s["private"], 16) for s in cv["server"]}
+        assert scalars >= {0, 1, 2, 3, n - 2, n - 1, n, n + 1, (n - 1) // 2, (n + 1) // 2, top - 1, top >> 1, top - n}
+        coords = {0, 1, 2, p - 2, p - 1, p, p + 1, top - 1, top >> 1, (1 << 96) - 1}
+        nb2 = 2 * c.num_bytes
+        assert {int(s["peer"][:nb2], 16) for s in cv["server"]} >= coords
+        assert {int(s["peer"][nb2:], 16) for s in cv["server"]} >= coords
+        assert {s["keylen"] for s in cv["server"]} == {16, 32}
+        assert 0 < sum(s["ok"] for s in cv["server"]) < len(cv["server"])
+
+
 def _ref_exe(name):
     p = os.path.join(ROOT, "oracle", "_ref", name)
     if not os.access(p, os.X_OK):
