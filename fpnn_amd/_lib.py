@@ -114,6 +114,8 @@ SIGNATURES = {
     "fpnn_aes_package_decrypt": (C.c_int, [_vp, C.POINTER(BatchDesc)]),
     "fpnn_aes_stream_encrypt": (C.c_int, [_vp, C.POINTER(BatchDesc), _vp, _vp]),
     "fpnn_aes_stream_decrypt": (C.c_int, [_vp, C.POINTER(BatchDesc), _vp, _vp]),
+    "fpnn_aes_stream_encrypt_frames": (C.c_int, [_vp, C.POINTER(BatchDesc), _vp, C.c_uint32, _vp, _vp]),
+    "fpnn_aes_stream_decrypt_frames": (C.c_int, [_vp, C.POINTER(BatchDesc), _vp, C.c_uint32, _vp, _vp]),
     "fpnn_aes_cfb_host": (C.c_int, [_vp, C.POINTER(Schedule), C.c_int, _vp, _vp, C.c_size_t, _u8p,
                                     C.POINTER(C.c_size_t)]),
     "fpnn_aes_package_host": (C.c_int, [_vp, C.c_int, C.POINTER(HostFrame), C.c_uint32, _vp, C.c_uint32]),

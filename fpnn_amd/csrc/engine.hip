@@ -269,6 +269,16 @@ struct fpnn_aes_engine {
     uint32_t *d_desc_len = nullptr;
     uint64_t cap_desc_len = 0;
     uint64_t *d_total = nullptr;  // ragged block total (bstart[count]), device only
+    // *_frames decrypt (k_stream_frames.hip), per segment: the stream it belongs to, the
+    // stream's last non-empty frame before it, and the state K1r exports for it
+    uint32_t *d_sf_stream = nullptr;
+    uint64_t cap_sf_stream = 0;
+    uint32_t *d_sf_prev = nullptr;
+    uint64_t cap_sf_prev = 0;
+    uint4 *d_sf_iv = nullptr;
+    uint64_t cap_sf_iv = 0;
+    uint32_t *d_sf_pos = nullptr;
+    uint64_t cap_sf_pos = 0;
     uint64_t *d_lookback = nullptr;  // one-pass block map: tickets, epoch, tile status (zeroed when grown)
     uint64_t cap_lookback = 0;
     // device-side consistency checks (kFault*): a pinned word kernels may set, read when the
@@ -403,6 +413,7 @@ int stream_idle(fpnn_aes_engine *e) {
         (void)hipMemsetAsync(e->d_buckets, 0, e->cap_buckets * sizeof(uint32_t), e->stream);
     g_last_error = (f & kFaultLookback)      ? "block map: a look-back gave up waiting for a tile (results of that call invalid)"
                    : (f & kFaultLengthOrder) ? "length order: bucket counts did not add up to the batch (results of that call invalid)"
+                   : (f & kFaultFrameTable)  ? "first_frame: not non-decreasing from 0 to count (results of that call invalid)"
                                              : "device-side check failed";
     return FPNN_AES_ERR_DEVICE;
 }
@@ -494,8 +505,10 @@ bool is_uniform_layout(const fpnn_aes_batch *b) {
 // Before an encrypt call: the extents of every buffer the call's kernels may touch, in the
 // engine's table (synchronous; the audit build is a checker, not a product).  The scratch
 // the call grows is grown here first so that its extent is known.
+// frames: a *_frames call -- first_frame[] is registered and the state arrays hold one entry
+// per stream.
 int audit_begin(fpnn_aes_engine *e, const fpnn_aes_batch *b, const uint8_t *iv_state, const uint32_t *pos_state,
-                KBatch &k) {
+                KBatch &k, const FrameTable *frames = nullptr) {
     int rc;
     if (!e->d_aud) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->d_aud), sizeof(AuditTable)));
     if ((rc = grow(e, e->d_perm, e->cap_perm, b->count))) return rc;
@@ -520,9 +533,11 @@ int audit_begin(fpnn_aes_engine *e, const fpnn_aes_batch *b, const uint8_t *iv_s
     const uint64_t slots = std::max<uint64_t>(b->keys->count, b->keys->capacity);
     set(AB_KEYS, b->keys->d_keys, sizeof(DevKey) * slots);
     set(AB_EIV, b->keys->d_eiv, 16 * slots);
-    set(AB_IV_STATE, iv_state, 16 * n);
-    set(AB_POS_STATE, pos_state, 4 * n);
-    set(AB_POS_SNAP, pos_state, 4 * n);
+    const uint64_t nstate = frames ? frames->nstreams : n;
+    set(AB_IV_STATE, iv_state, 16 * nstate);
+    set(AB_POS_STATE, pos_state, 4 * nstate);
+    set(AB_POS_SNAP, pos_state, 4 * nstate);
+    if (frames) set(AB_FIRST_FRAME, frames->first_frame, 4 * ((uint64_t)frames->nstreams + 1));
     set(AB_PERM, e->d_perm, 4 * n);
     set(AB_SINK, e->d_sink, 16 * e->cap_sink);
     set(AB_BLOCK, e->d_buckets, 4 * (uint64_t)kLengthOrderWords);
@@ -563,7 +578,8 @@ int audit_begin(fpnn_aes_engine *e, const fpnn_aes_batch *b, const uint8_t *iv_s
 const char *audit_buf_name(uint32_t i) {
     static const char *const names[kAuditBufs] = {"in", "out", "in_off", "out_off", "len", "key_slot", "keys", "eiv",
                                                   "iv_state", "pos_state", "perm", "sink", "length-order block",
-                                                  "pos_snap", "in (outside its segment)", "out (outside its segment)"};
+                                                  "pos_snap", "in (outside its segment)", "out (outside its segment)",
+                                                  "first_frame"};
     return i < kAuditBufs ? names[i] : "?";
 }
 
@@ -818,6 +834,131 @@ int run_decrypt(fpnn_aes_engine *e, const fpnn_aes_batch *b, uint8_t *iv_state, 
     return timing_end(e, ev, FPNN_AES_K_DECRYPT);
 }
 
+// ---- many frames per stream in one call (fpnn_aes_stream_*_frames, k_stream_frames.hip) ----
+
+int check_frames(const fpnn_aes_engine *e, const fpnn_aes_batch *b, const uint32_t *first_frame, uint32_t nstreams,
+                 const uint8_t *iv_state, const uint32_t *pos_state) {
+    const int rc = check_batch(e, b);
+    if (rc) return rc;
+    if (b->flags & FPNN_AES_F_WIRE_PREFIX) return FPNN_AES_ERR_ARG;
+    if (nstreams && (!first_frame || !iv_state || !pos_state || ((uintptr_t)iv_state & 15) ||
+                     ((uintptr_t)pos_state & 3) || ((uintptr_t)first_frame & 3)))
+        return FPNN_AES_ERR_ARG;
+    return FPNN_AES_OK;
+}
+
+// Encrypt: K2f, one quad per stream, sized as K2c is (by quads needed, at most one workgroup
+// per CU; further streams grid-stride).  Streams are visited in index order: no length order.
+int run_encrypt_frames_calls(fpnn_aes_engine *e, const fpnn_aes_batch *b, const uint32_t *first_frame,
+                             uint32_t nstreams, uint8_t *iv_state, uint32_t *pos_state) {
+    int rc = check_frames(e, b, first_frame, nstreams, iv_state, pos_state);
+    if (rc) return rc;
+    if (!nstreams || !b->count) return FPNN_AES_OK;
+    DeviceGuard g(e->device);
+    const BatchScope batch_scope(e);  // (an early return clears the pending flag)
+    KBatch k = make_kbatch(e, b, iv_state, pos_state);
+    const FrameTable f{first_frame, nstreams, 0u, e->d_fault};
+#ifdef FPNN_AES_BOUNDS
+    if ((rc = audit_begin(e, b, iv_state, pos_state, k, &f))) return rc;
+#endif
+    const KeyMode km = (b->key_slot && b->keys->count > 1) ? KEY_LANE : KEY_UNIFORM;
+    const uint64_t lanes = 4ull * nstreams;
+    int threads = 64;
+    while (threads < kThreads && (uint64_t)threads * e->num_cus < lanes) threads *= 2;
+    const uint64_t want = (lanes + threads - 1) / threads;
+    const int grid = (int)(want < (uint64_t)e->num_cus ? want : (uint64_t)e->num_cus);
+    EventPair *ev;
+    if ((rc = timing_begin(e, FPNN_AES_K_ENCRYPT, &ev))) return rc;
+    HIP_TRY(launch_encrypt_stream_frames(k, f, b->keys->nrounds, km, grid, threads, e->stream));
+    return timing_end(e, ev, FPNN_AES_K_ENCRYPT);
+}
+
+// Decrypt: the state pre-pass fills K1r's per-segment snapshot, K1r decrypts every block in
+// parallel and exports each segment's outgoing state into per-segment scratch, the commit
+// gives every stream its last non-empty frame's.  The caller's state arrays are read by
+// the pre-pass and K1r's plan only through the snapshot, and written by the commit alone.
+int run_decrypt_frames_calls(fpnn_aes_engine *e, const fpnn_aes_batch *b, const uint32_t *first_frame,
+                             uint32_t nstreams, uint8_t *iv_state, uint32_t *pos_state) {
+    int rc = check_frames(e, b, first_frame, nstreams, iv_state, pos_state);
+    if (rc) return rc;
+    if (!nstreams || !b->count) return FPNN_AES_OK;
+    DeviceGuard g(e->device);
+    const BatchScope batch_scope(e);
+    const uint64_t n = b->count;
+    const int grid = e->num_cus;
+    // (everything that can fail first: nothing is queued before the scratch stands)
+    if ((rc = grow(e, e->d_snap_iv, e->cap_snap_iv, n))) return rc;
+    if ((rc = grow(e, e->d_snap_pos, e->cap_snap_pos, n))) return rc;
+    if ((rc = grow(e, e->d_sf_stream, e->cap_sf_stream, n))) return rc;
+    if ((rc = grow(e, e->d_sf_prev, e->cap_sf_prev, n))) return rc;
+    if ((rc = grow(e, e->d_sf_iv, e->cap_sf_iv, n))) return rc;
+    if ((rc = grow(e, e->d_sf_pos, e->cap_sf_pos, n))) return rc;
+    if ((rc = grow(e, e->d_bstart, e->cap_bstart, n + 1))) return rc;
+    if ((rc = grow(e, e->d_plan, e->cap_plan, (uint64_t)grid * (kThreads / 64)))) return rc;
+    if ((rc = grow(e, e->d_sink, e->cap_sink, 2ull * grid * (kThreads / 64)))) return rc;
+    if (!b->in_off && (rc = grow(e, e->d_desc_off, e->cap_desc_off, n))) return rc;
+    if (!b->len && (rc = grow(e, e->d_desc_len, e->cap_desc_len, n))) return rc;
+    const bool small_map = n <= block_map_small_max();
+    if (!small_map && block_map_onepass_words(n) > e->cap_lookback) {  // the kernel expects zeros on first use
+        if ((rc = grow(e, e->d_lookback, e->cap_lookback, block_map_onepass_words(n)))) return rc;
+        HIP_TRY(hipMemsetAsync(e->d_lookback, 0, e->cap_lookback * sizeof(uint64_t), e->stream));
+    }
+    KBatch k = make_kbatch(e, b, iv_state, pos_state);
+    const FrameTable f{first_frame, nstreams, 0u, e->d_fault};
+#ifdef FPNN_AES_BOUNDS
+    if ((rc = audit_begin(e, b, iv_state, pos_state, k, &f))) return rc;
+#endif
+    const KeyMode km = (b->key_slot && b->keys->count > 1) ? KEY_LANE : KEY_UNIFORM;
+    // the pre-pass reads the ciphertext and the incoming state: before the block map (whose
+    // block counts read pos_snap) and before any in-place write
+    HIP_TRY(launch_stream_frames_state(k, f, b->keys->nrounds, km, e->d_snap_iv, e->d_snap_pos, e->d_sf_stream,
+                                       e->d_sf_prev, e->num_cus, e->stream));
+    k.iv_snap = e->d_snap_iv;
+    k.pos_snap = e->d_snap_pos;
+    // from here on "the state" is per segment: K1r exports into the scratch
+    k.iv_state = reinterpret_cast<uint8_t *>(e->d_sf_iv);
+    k.pos_state = e->d_sf_pos;
+    if (small_map)
+        // (its snapshot copy goes from the pre-pass's snapshot into the export scratch, which
+        // K1r overwrites: the snapshot itself stays as the pre-pass wrote it)
+        HIP_TRY(launch_block_map_small(k, true, reinterpret_cast<const uint8_t *>(e->d_snap_iv), e->d_snap_pos, e->d_sf_iv,
+                                       e->d_sf_pos, e->d_bstart, e->d_total, e->stream));
+    else
+        HIP_TRY(launch_block_map_onepass(k, true, e->d_bstart, e->d_lookback, e->cap_lookback, e->d_fault, e->d_total,
+                                         e->stream));
+    k.bstart = e->d_bstart;
+    if (!k.in_off || !k.len) {  // K1r reads descriptor arrays: materialize the missing ones
+        HIP_TRY(launch_ragged_desc(n, b->stride, b->uniform_len, k.in_off ? nullptr : e->d_desc_off,
+                                   k.len ? nullptr : e->d_desc_len, e->stream));
+        if (!k.in_off) k.in_off = e->d_desc_off;
+        if (!k.len) k.len = e->d_desc_len;
+    }
+    if (!k.out_off) k.out_off = k.in_off;
+    k.runs = (uint32_t)e->variant.k1r_runs;
+    EventPair *ev = nullptr;
+    if ((rc = timing_begin(e, FPNN_AES_K_DECRYPT, &ev))) return rc;
+    HIP_TRY(launch_decrypt_ragged(k, b->keys->nrounds, km, true, e->d_plan, e->d_sink, b->in == b->out, grid,
+                                  e->stream));
+    if ((rc = timing_end(e, ev, FPNN_AES_K_DECRYPT))) return rc;
+    k.iv_state = iv_state;
+    k.pos_state = pos_state;
+    k.len = b->len;  // (as the caller gave it: uniform_len otherwise)
+    HIP_TRY(launch_stream_frames_commit(k, f, e->d_sf_iv, e->d_sf_pos, e->stream));
+    batch_queued(e);  // (the call's batch work ends behind the commit)
+    return FPNN_AES_OK;
+}
+
+int run_frames(fpnn_aes_engine *e, const fpnn_aes_batch *b, const uint32_t *first_frame, uint32_t nstreams,
+               uint8_t *iv_state, uint32_t *pos_state, bool encrypt) {
+    const int rc = encrypt ? run_encrypt_frames_calls(e, b, first_frame, nstreams, iv_state, pos_state)
+                           : run_decrypt_frames_calls(e, b, first_frame, nstreams, iv_state, pos_state);
+#ifdef FPNN_AES_BOUNDS
+    return audit_end(e, rc);
+#else
+    return rc;
+#endif
+}
+
 }  // namespace
 
 // ===========================================================================
@@ -833,7 +974,8 @@ const char *fpnn_aes_version(void) {
     return "fpnn_aes 0.4 (gfx950; T-tables 32-way replicated in LDS; v_perm addressing; "
            "decrypt: K1d dense/keyed, K1k lane keys, K1r ragged (no host sync; interior runs), K1 uniform, "
            "one lane per block; encrypt: K2 lane per chain, K2c quad per chain, K2h lanes + quads for ragged "
-           "batches; single calls <= 16 KiB: K0s resident server (K0 per launch); "
+           "batches, K2f quad per stream over many frames per call (stream_encrypt_frames; stream_decrypt_frames: "
+           "state pre-pass + K1r); single calls <= 16 KiB: K0s resident server (K0 per launch); "
            "ECDH: one lane per derivation, special-prime folds as carry chains)";
 }
 
@@ -958,7 +1100,8 @@ int fpnn_aes_engine_destroy(fpnn_aes_engine *e) {
                     (void *)e->d_snap_pos, (void *)e->d_perm, (void *)e->d_buckets,
                     (void *)e->d_fr_off, (void *)e->d_fr_slot, (void *)e->d_plan, (void *)e->d_sink,
                     (void *)e->d_desc_off, (void *)e->d_desc_len, (void *)e->d_ecdh, (void *)e->d_sstate,
-                    (void *)e->d_lookback})
+                    (void *)e->d_lookback, (void *)e->d_sf_stream, (void *)e->d_sf_prev, (void *)e->d_sf_iv,
+                    (void *)e->d_sf_pos})
         release_scratch(e, p);
     if (e->stream) (void)hipStreamSynchronize(e->stream);
     free_deferred(e);
@@ -1075,6 +1218,11 @@ int fpnn_aes_engine_reserve(fpnn_aes_engine *e, uint64_t max_segments, uint64_t 
     if ((rc = grow(e, e->d_snap_pos, e->cap_snap_pos, max_segments))) return rc;
     if ((rc = grow(e, e->d_desc_off, e->cap_desc_off, max_segments))) return rc;
     if ((rc = grow(e, e->d_desc_len, e->cap_desc_len, max_segments))) return rc;
+    // the *_frames decrypt pre-pass and K1r's per-segment state
+    if ((rc = grow(e, e->d_sf_stream, e->cap_sf_stream, max_segments))) return rc;
+    if ((rc = grow(e, e->d_sf_prev, e->cap_sf_prev, max_segments))) return rc;
+    if ((rc = grow(e, e->d_sf_iv, e->cap_sf_iv, max_segments))) return rc;
+    if ((rc = grow(e, e->d_sf_pos, e->cap_sf_pos, max_segments))) return rc;
     return FPNN_AES_OK;
 }
 
@@ -1292,6 +1440,16 @@ int fpnn_aes_stream_encrypt(fpnn_aes_engine *e, const fpnn_aes_batch *b, uint8_t
 
 int fpnn_aes_stream_decrypt(fpnn_aes_engine *e, const fpnn_aes_batch *b, uint8_t *iv_state, uint32_t *pos_state) {
     return run_decrypt(e, b, iv_state, pos_state, true);
+}
+
+int fpnn_aes_stream_encrypt_frames(fpnn_aes_engine *e, const fpnn_aes_batch *b, const uint32_t *first_frame,
+                                   uint32_t nstreams, uint8_t *iv_state, uint32_t *pos_state) {
+    return run_frames(e, b, first_frame, nstreams, iv_state, pos_state, true);
+}
+
+int fpnn_aes_stream_decrypt_frames(fpnn_aes_engine *e, const fpnn_aes_batch *b, const uint32_t *first_frame,
+                                   uint32_t nstreams, uint8_t *iv_state, uint32_t *pos_state) {
+    return run_frames(e, b, first_frame, nstreams, iv_state, pos_state, false);
 }
 
 // ---- receive side: wire framing on the device ------------------------------------

@@ -130,6 +130,35 @@ hipError_t launch_decrypt_frames(const KBatch &b, int nrounds, KeyMode km, int g
 // K2c: one 4-lane quad per chain (few / long chains); threads = workgroup size.
 hipError_t launch_encrypt_coop(const KBatch &b, int nrounds, Layout layout, KeyMode km, bool stream, int grid,
                                int threads, hipStream_t st);
+// Stream batches that carry many frames per stream (k_stream_frames.hip;
+// fpnn_aes_stream_*_frames): stream j owns segments [first_frame[j], first_frame[j+1]) and
+// b.iv_state / b.pos_state hold nstreams entries.  Every kernel clamps what it reads from
+// first_frame into [0, count] (an empty range when it decreases) and stores
+// kFaultFrameTable into *fault when the table is not monotone from 0 to count.
+struct FrameTable {
+    const uint32_t *first_frame;  // nstreams + 1 entries
+    uint32_t nstreams;
+    uint32_t pad;
+    uint32_t *fault;
+};
+// K2f: encrypt, one quad per STREAM (K2c's cipher); the quad keeps (iv, pos) in registers
+// across the stream's frames; grid and threads sized as K2c's, by quads needed.
+hipError_t launch_encrypt_stream_frames(const KBatch &b, const FrameTable &f, int nrounds, KeyMode km, int grid,
+                                        int threads, hipStream_t st);
+// Decrypt: the state pre-pass.  K1r reads every segment's incoming (iv, pos) from
+// b.iv_snap / b.pos_snap; these two launches fill that snapshot (snap_iv, snap_pos; count
+// entries) from the streams' incoming state and the ciphertext alone, before anything is
+// written: one lane per stream walks its frames' lengths (snap_pos, and per segment its
+// stream and the last non-empty frame before it: seg_stream, seg_prev), then one lane per
+// segment gathers the ciphertext block before its frame and runs at most one AES pass.
+hipError_t launch_stream_frames_state(const KBatch &b, const FrameTable &f, int nrounds, KeyMode km, uint4 *snap_iv,
+                                      uint32_t *snap_pos, uint32_t *seg_stream, uint32_t *seg_prev, int num_cus,
+                                      hipStream_t st);
+// After K1r, which exported every non-empty segment's outgoing state into seg_iv / seg_pos
+// (per SEGMENT): stream j's state becomes that of its last non-empty frame; a stream
+// without one keeps its own.
+hipError_t launch_stream_frames_commit(const KBatch &b, const FrameTable &f, const uint4 *seg_iv,
+                                       const uint32_t *seg_pos, hipStream_t st);
 // K2h (k_hybrid.hip): ragged batches with more chains than quads.  Chains of perm[]
 // in length buckets <= long_bucket run on quads (K2c's cipher), the rest one per lane
 // (K2's); quad_waves waves per workgroup start on the long ones.  ctr: the 2 ticket
@@ -195,6 +224,7 @@ hipError_t launch_boundary_save(const KBatch &b, uint4 *boundary, uint64_t nchun
 // gave up waiting (the host reports FPNN_AES_ERR_DEVICE at the next sync).
 constexpr uint32_t kFaultLookback = 1u;
 constexpr uint32_t kFaultLengthOrder = 2u;
+constexpr uint32_t kFaultFrameTable = 4u;  // a first_frame table not monotone from 0 to count (FrameTable)
 uint64_t block_map_onepass_words(uint64_t count);
 hipError_t launch_block_map_onepass(const KBatch &b, bool stream, uint64_t *bstart, uint64_t *lb, uint64_t lb_words,
                                     uint32_t *fault, uint64_t *total, hipStream_t st);

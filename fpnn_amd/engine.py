@@ -365,6 +365,28 @@ class Engine:
         d = self._desc(inp, out, count, keys, **kw)
         check(lib.fpnn_aes_stream_decrypt(self._h, C.byref(d), _ptr(iv_state), _ptr(pos_state)), "stream_decrypt")
 
+    # Many frames of each stream in one call: stream j owns segments [first_frame[j],
+    # first_frame[j + 1]) of the batch, its frames in order; the state arrays hold nstreams
+    # entries (fpnn_aes_stream_encrypt_frames / _decrypt_frames).
+    def _frames(self, fn, what, inp, out, count, keys, iv_state, pos_state, first_frame, nstreams, kw):
+        d = self._desc(inp, out, count, keys, **kw)
+        if first_frame is not None:
+            if first_frame.dtype not in (torch.int32, torch.uint32):
+                raise TypeError(f"first_frame: dtype {first_frame.dtype}, expected {torch.int32}")
+            if first_frame.numel() < nstreams + 1:
+                raise ValueError(f"first_frame: {first_frame.numel()} entries for {nstreams} streams")
+        check(fn(self._h, C.byref(d), _ptr(first_frame), nstreams, _ptr(iv_state), _ptr(pos_state)), what)
+
+    def stream_encrypt_frames(self, inp, out, count, keys: "KeySet", iv_state: torch.Tensor, pos_state: torch.Tensor,
+                              first_frame: torch.Tensor, nstreams: int, **kw):
+        self._frames(lib.fpnn_aes_stream_encrypt_frames, "stream_encrypt_frames", inp, out, count, keys, iv_state,
+                     pos_state, first_frame, nstreams, kw)
+
+    def stream_decrypt_frames(self, inp, out, count, keys: "KeySet", iv_state: torch.Tensor, pos_state: torch.Tensor,
+                              first_frame: torch.Tensor, nstreams: int, **kw):
+        self._frames(lib.fpnn_aes_stream_decrypt_frames, "stream_decrypt_frames", inp, out, count, keys, iv_state,
+                     pos_state, first_frame, nstreams, kw)
+
 
 def host_register(buf: np.ndarray):
     """fpnn_aes_host_register over a numpy buffer's memory (e.g. a socket-buffer arena):

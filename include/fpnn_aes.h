@@ -88,7 +88,8 @@ void *fpnn_aes_engine_stream(fpnn_aes_engine *e);
  * (hipStreamBeginCapture) may be replayed with new data, offsets and lengths in the same
  * device arrays, because every piece of cross-call scratch state (the block map's
  * look-back epoch and tickets, the length-order block and K2h's tickets) is reset on the
- * device by the kernels that use it (tests/test_gpu_graph.py). */
+ * device by the kernels that use it (tests/test_gpu_graph.py).  The *_frames stream calls'
+ * per-segment scratch is sized from max_segments as well. */
 int fpnn_aes_engine_reserve(fpnn_aes_engine *e, uint64_t max_segments, uint64_t max_blocks);
 
 /* Placement of the engines behind the C++ classes (Encryptor, EncryptorBatch,
@@ -181,11 +182,31 @@ int fpnn_aes_package_decrypt(fpnn_aes_engine *e, const fpnn_aes_batch *b);
 /* Segment i continues the CFB stream whose state is (iv_state[16*i .. +16],
  * pos_state[i]) -- StreamEncryptor::_iv and ::_pos -- with key slot slot_i; the
  * state is updated in place (dev arrays).  A given stream must appear at most once
- * per call; successive frames of a stream go in successive calls. */
+ * per call; successive frames of a stream go in successive calls of these two -- or all
+ * in one call of the *_frames pair below. */
 int fpnn_aes_stream_encrypt(fpnn_aes_engine *e, const fpnn_aes_batch *b, uint8_t *iv_state,
                             uint32_t *pos_state);
 int fpnn_aes_stream_decrypt(fpnn_aes_engine *e, const fpnn_aes_batch *b, uint8_t *iv_state,
                             uint32_t *pos_state);
+
+/* Many frames of each stream in one call (a connection's send queue holds several frames
+ * per IO cycle, core/IOBuffer.cpp:47-74).  Stream j owns segments [first_frame[j],
+ * first_frame[j+1]) of b, its frames in order: first_frame[0] == 0, first_frame[nstreams]
+ * == b->count, non-decreasing.  Results and the final state equal that many successive
+ * StreamEncryptor::encrypt / decrypt calls on (iv_state[16*j .. +16], pos_state[j]); the
+ * state arrays have nstreams entries, indexed by stream (not by segment).  A stream with no
+ * segments, or only empty ones, keeps its state bit for bit.  Segments are described as in
+ * every batch (anywhere, in any memory order, with gaps; in place as above); key_slot[] stays
+ * per segment, all frames of a stream must name the same slot and the kernels read any one
+ * of them.  FPNN_AES_F_WIRE_PREFIX, a NULL first_frame, NULL or misaligned state with
+ * nstreams != 0: FPNN_AES_ERR_ARG.  nstreams == 0 or b->count == 0 queues nothing.  Queue-
+ * only like the pair above.  A first_frame that is not monotone or does not span [0, count]
+ * never makes a kernel leave the batch (what is read from it is clamped): the call's results
+ * are then invalid and the next fpnn_aes_engine_sync returns FPNN_AES_ERR_DEVICE. */
+int fpnn_aes_stream_encrypt_frames(fpnn_aes_engine *e, const fpnn_aes_batch *b, const uint32_t *first_frame,
+                                   uint32_t nstreams, uint8_t *iv_state, uint32_t *pos_state);
+int fpnn_aes_stream_decrypt_frames(fpnn_aes_engine *e, const fpnn_aes_batch *b, const uint32_t *first_frame,
+                                   uint32_t nstreams, uint8_t *iv_state, uint32_t *pos_state);
 
 /* ---- single call from host memory (the per-frame drop-in) --------------------------- */
 /* Exactly rijndael_cfb_encrypt(ctx, encrypt, in, out, len, ivec, p_num)

@@ -4,7 +4,8 @@ for DESIGN.md -- bench.py's single JSON line covers C2 only.
 
   C2  1M x 1 KiB AES-256 package                    (also: PCIe-inclusive rate)
   C3  4096 streams x 4 MiB AES-128 stream mode      (whole stream per call, and cut into
-                                                      random 1 B..64 KiB frames = one call per frame round)
+                                                      random 1 B..64 KiB frames = one call per frame round,
+                                                      and all those rounds as one *_frames call)
   C4  Zipf 64 B..64 KiB, 4 GiB, AES-256 package
   C5  65536 keys x 4 KiB AES-256, per-key IV
   U1  1M x 1472 B UDP datagrams over 16384 connections, AES-128
@@ -400,12 +401,36 @@ def main():
         wfe, kfe, nfe = timed(eng, E, lambda: framed(eng.stream_encrypt, a, b), args.reps)
         wfd, kfd, nfd = timed(eng, D, lambda: framed(eng.stream_decrypt, b, r), args.reps)
         assert torch.equal(r, a)
+        # the same frame rounds submitted as ONE *_frames call: segments ordered by stream,
+        # first_frame from the split counts
+        one_lens = np.concatenate([np.asarray(x, dtype=np.int32) for x in splits])
+        one_first = np.concatenate([[0], np.cumsum([len(x) for x in splits])]).astype(np.int32)
+        one_offs = np.concatenate([s_ * L + np.concatenate([[0], np.cumsum(x[:-1])]).astype(np.int64)
+                                   for s_, x in enumerate(splits)])
+        nseg = int(one_first[-1])
+        d1_lens, d1_offs, d1_first = (torch.from_numpy(x).cuda() for x in (one_lens, one_offs, one_first))
+        d1_slots = torch.repeat_interleave(slots, torch.from_numpy(np.diff(one_first)).cuda())
+        eng.reserve(nseg, S * L // 16 + nseg)
+
+        def onecall(fn, src, dst):
+            st_iv.copy_(iv0)
+            st_pos.zero_()
+            fn(src, dst, nseg, ks, st_iv, st_pos, d1_first, S, in_off=d1_offs, lens=d1_lens, key_slot=d1_slots)
+
+        woe, koe, _ = timed(eng, E, lambda: onecall(eng.stream_encrypt_frames, a, r), args.reps)
+        assert torch.equal(r, b)  # (b: the per-round calls' ciphertext)
+        wod, kod, _ = timed(eng, D, lambda: onecall(eng.stream_decrypt_frames, b, r), args.reps)
+        assert torch.equal(r, a)
+        one = {"framed_onecall_segments": nseg, "framed_onecall_encrypt_wall_GiBs": gib(S * L, woe),
+               "framed_onecall_encrypt_kernel_GiBs": gib(S * L, koe),
+               "framed_onecall_decrypt_wall_GiBs": gib(S * L, wod),
+               "framed_onecall_decrypt_kernel_GiBs": gib(S * L, kod)}
         if args.no_host:
             out["C3"] = {"whole_stream_encrypt_kernel_GiBs": gib(S * L, ke),
                          "whole_stream_decrypt_kernel_GiBs": gib(S * L, kd),
                          "framed_calls": nmax, "framed_encrypt_wall_GiBs": gib(S * L, wfe),
                          "framed_decrypt_wall_GiBs": gib(S * L, wfd),
-                         "framed_decrypt_kernel_GiBs": gib(S * L, kfd * nfd)}
+                         "framed_decrypt_kernel_GiBs": gib(S * L, kfd * nfd), **one}
             print(json.dumps({"C3": out["C3"]}), flush=True)
             todo = [t for t in todo if t != "C3"]
     if "C3" in todo:
@@ -437,7 +462,7 @@ def main():
                      "whole_stream_decrypt_kernel_GiBs": gib(S * L, kd),
                      "framed_calls": nmax, "framed_encrypt_wall_GiBs": gib(S * L, wfe),
                      "framed_decrypt_wall_GiBs": gib(S * L, wfd),
-                     "framed_decrypt_kernel_GiBs": gib(S * L, kfd * nfd),
+                     "framed_decrypt_kernel_GiBs": gib(S * L, kfd * nfd), **one,
                      "host_frames_streams": HS, "host_frames": len(fl),
                      "host_frames_encrypt_GiBs": gib(HS * L, hse), "host_frames_decrypt_GiBs": gib(HS * L, hsd),
                      "note": "encrypt = 4096 serial CFB chains (one lane each, latency bound); "
