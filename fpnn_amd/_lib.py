@@ -110,6 +110,9 @@ SIGNATURES = {
     "fpnn_aes_keyset_count": (C.c_uint32, [_vp]),
     "fpnn_aes_keyset_nrounds": (C.c_int, [_vp]),
     "fpnn_aes_keyset_get_schedule": (C.c_int, [_vp, C.c_uint32, C.POINTER(Schedule)]),
+    "fpnn_aes_keyset_capacity": (C.c_uint32, [_vp]),
+    "fpnn_aes_keyset_set_keys": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _vp, C.c_uint32, _vp, _vp, _vp]),
+    "fpnn_aes_keyset_clear": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _vp, C.c_uint32]),
     "fpnn_aes_package_encrypt": (C.c_int, [_vp, C.POINTER(BatchDesc)]),
     "fpnn_aes_package_decrypt": (C.c_int, [_vp, C.POINTER(BatchDesc)]),
     "fpnn_aes_stream_encrypt": (C.c_int, [_vp, C.POINTER(BatchDesc), _vp, _vp]),
@@ -145,6 +148,7 @@ SIGNATURES = {
     "fpnn_ecdh_calc_keys_client": (C.c_int, [_vp, C.c_int, _vp, C.c_char_p, C.c_uint32, C.c_int, _vp, _vp, _vp]),
     "fpnn_ecdh_public_keys": (C.c_int, [_vp, C.c_int, _vp, C.c_uint32, _vp, _vp]),
     "fpnn_ecdh_keyset": (C.c_int, [_vp, C.c_int, C.c_char_p, _vp, C.c_uint32, C.c_int, _vp, C.POINTER(_vp)]),
+    "fpnn_ecdh_accept": (C.c_int, [_vp, C.c_int, C.c_char_p, _vp, C.c_uint32, _vp, C.c_uint32, _vp, C.c_uint32, _vp]),
     "fpnn_ecdh_calc_keys_host": (C.c_int, [_vp, C.c_int, C.c_char_p, C.c_char_p, C.c_uint32, C.c_int, _vp, _vp,
                                            _vp]),
     "fpnn_ecdh_calc_key_host": (C.c_int, [_vp, C.c_char_p, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_int,

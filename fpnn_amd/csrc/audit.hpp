@@ -2,9 +2,10 @@
 // fpnn_amd/libfpnn_aes_gpu_audit.so, compiled with -DFPNN_AES_BOUNDS).
 //
 // Every global load and store of K2h (k_hybrid.hip), K2's ragged path (k_encrypt.hip), the
-// length-order kernels (k_support.hip) and the many-frames-per-stream kernels
-// (k_stream_frames.hip: the caller's arrays and the payload) names the buffer it indexes
-// through FA_AT / FA_SEG / FA_RG.  In the audit build each one checks its byte range against an extent:
+// length-order kernels (k_support.hip), the many-frames-per-stream kernels
+// (k_stream_frames.hip: the caller's arrays and the payload) and the key-table writes
+// (k_keytable.hip: the caller's arrays, the DevKey slots and eiv[]) names the buffer it
+// indexes through FA_AT / FA_SEG / FA_RG.  In the audit build each one checks its byte range against an extent:
 //   * the array extents the host supplies per call (AuditTable::lo/hi: descriptor arrays of
 //     `count` entries, the key set's slots, perm[] of `count` entries, the wave sinks, the
 //     length-order block, the stream state arrays, and the union of the segments' payload);
@@ -40,6 +41,10 @@ enum AuditBuf : uint32_t {
     AB_SEG_OUT,    // payload written outside the current segment (+ wire prefix)
     AB_FIRST_FRAME,  // *_frames calls: first_frame[], nstreams + 1 entries (the state arrays then
                      // hold nstreams entries)
+    AB_KT_SLOTS,   // key-table writes (k_keytable.hip): slots[], raw keys, IVs and ok[] of `count` entries
+    AB_KT_RAW,
+    AB_KT_IVS,
+    AB_KT_OK,
     kAuditBufs
 };
 

@@ -285,7 +285,8 @@ struct fpnn_aes_engine {
     // stream is idle (fpnn_aes_engine_sync, synchronous calls) and reported as FPNN_AES_ERR_DEVICE
     uint32_t *h_fault = nullptr;
     uint32_t *d_fault = nullptr;
-    uint8_t *d_ecdh = nullptr;  // ECDH host forms / keyset: peers | keys | ivs | ok (grown, kept)
+    uint8_t *d_ecdh = nullptr;  // ECDH host forms / keyset / accept: peers | keys | ivs | ok (grown, kept; every
+                                // call zeroes what it used once its last reader is queued: ecdh_wipe)
     uint64_t cap_ecdh = 0;
     uint8_t *d_sstate = nullptr;  // stream host frames: (iv, pos) of the call's streams (grown, kept)
     uint64_t cap_sstate = 0;
@@ -355,6 +356,10 @@ const uint8_t *sbox_of(const fpnn_aes_engine *e) { return e->d_tables + 1024; }
 const uint32_t *td0le_of(const fpnn_aes_engine *e) { return reinterpret_cast<const uint32_t *>(e->d_tables + 1280); }
 const uint8_t *isbox_of(const fpnn_aes_engine *e) { return e->d_tables + 2304; }
 
+// slots the table's allocations hold (a key set made by _create / _from_schedules has no
+// capacity of its own until it grows)
+uint32_t table_slots(const fpnn_aes_keyset *ks) { return std::max(ks->capacity, ks->count); }
+
 struct DeviceGuard {
     int prev = -1;
     explicit DeviceGuard(int dev) {
@@ -414,6 +419,7 @@ int stream_idle(fpnn_aes_engine *e) {
     g_last_error = (f & kFaultLookback)      ? "block map: a look-back gave up waiting for a tile (results of that call invalid)"
                    : (f & kFaultLengthOrder) ? "length order: bucket counts did not add up to the batch (results of that call invalid)"
                    : (f & kFaultFrameTable)  ? "first_frame: not non-decreasing from 0 to count (results of that call invalid)"
+                   : (f & kFaultKeySlot)     ? "key table: a slot index at or past slot_bound (that entry was not written)"
                                              : "device-side check failed";
     return FPNN_AES_ERR_DEVICE;
 }
@@ -579,7 +585,7 @@ const char *audit_buf_name(uint32_t i) {
     static const char *const names[kAuditBufs] = {"in", "out", "in_off", "out_off", "len", "key_slot", "keys", "eiv",
                                                   "iv_state", "pos_state", "perm", "sink", "length-order block",
                                                   "pos_snap", "in (outside its segment)", "out (outside its segment)",
-                                                  "first_frame"};
+                                                  "first_frame", "slots", "raw keys", "ivs", "ok"};
     return i < kAuditBufs ? names[i] : "?";
 }
 
@@ -976,7 +982,8 @@ const char *fpnn_aes_version(void) {
            "one lane per block; encrypt: K2 lane per chain, K2c quad per chain, K2h lanes + quads for ragged "
            "batches, K2f quad per stream over many frames per call (stream_encrypt_frames; stream_decrypt_frames: "
            "state pre-pass + K1r); single calls <= 16 KiB: K0s resident server (K0 per launch); "
-           "ECDH: one lane per derivation, special-prime folds as carry chains)";
+           "ECDH: one lane per derivation, special-prime folds as carry chains; "
+           "live key table: keyset_set_keys / keyset_clear / ecdh_accept, one lane per slot, queued)";
 }
 
 int fpnn_aes_setup_encrypt(fpnn_aes_schedule *ctx, const uint8_t *key, size_t keylen) {
@@ -1223,6 +1230,8 @@ int fpnn_aes_engine_reserve(fpnn_aes_engine *e, uint64_t max_segments, uint64_t 
     if ((rc = grow(e, e->d_sf_prev, e->cap_sf_prev, max_segments))) return rc;
     if ((rc = grow(e, e->d_sf_iv, e->cap_sf_iv, max_segments))) return rc;
     if ((rc = grow(e, e->d_sf_pos, e->cap_sf_pos, max_segments))) return rc;
+    // fpnn_ecdh_accept of up to max_segments peers: key (<= 32) | iv (16) | ok (1) each
+    if ((rc = grow(e, e->d_ecdh, e->cap_ecdh, max_segments * (32 + 16 + 1)))) return rc;
     return FPNN_AES_OK;
 }
 
@@ -1241,6 +1250,7 @@ int fpnn_aes_keyset_create(fpnn_aes_engine *e, uint32_t count, size_t keylen, co
     ks->keylen = (uint32_t)keylen;
     ks->nrounds = (int)keylen / 4 + 6;
     uint8_t *d_raw = nullptr;
+    size_t raw_bytes = 0;
     int rc = FPNN_AES_OK;
     do {
         hipError_t err = hipMalloc(reinterpret_cast<void **>(&ks->d_keys), sizeof(DevKey) * (size_t)count);
@@ -1249,6 +1259,7 @@ int fpnn_aes_keyset_create(fpnn_aes_engine *e, uint32_t count, size_t keylen, co
         if (keys_on_host) {
             const size_t kb = (size_t)count * keylen, ib = ivs ? (size_t)count * 16 : 0;
             err = hipMalloc(reinterpret_cast<void **>(&d_raw), kb + ib);
+            raw_bytes = kb + ib;
             if (err == hipSuccess) err = hipMemcpy(d_raw, keys, kb, hipMemcpyHostToDevice);
             if (err == hipSuccess && ivs) err = hipMemcpy(d_raw + kb, ivs, ib, hipMemcpyHostToDevice);
             if (err != hipSuccess) { rc = hip_fail(err, "upload(keys)"); break; }
@@ -1262,7 +1273,11 @@ int fpnn_aes_keyset_create(fpnn_aes_engine *e, uint32_t count, size_t keylen, co
         if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
         if (err != hipSuccess) { rc = hip_fail(err, "expand_keys"); break; }
     } while (0);
-    if (d_raw) (void)hipFree(d_raw);
+    if (d_raw) {  // the raw keys' upload: wiped behind the expansion that read it, then freed
+        (void)hipMemsetAsync(d_raw, 0, raw_bytes, e->stream);
+        (void)hipStreamSynchronize(e->stream);
+        (void)hipFree(d_raw);
+    }
     if (rc) {
         fpnn_aes_keyset_destroy(ks);
         return rc;
@@ -1315,9 +1330,23 @@ int fpnn_aes_keyset_destroy(fpnn_aes_keyset *ks) {
         if (ks->up_pending) (void)hipEventSynchronize(ks->up_done);
         (void)hipEventDestroy(ks->up_done);
     }
-    if (ks->h_up) (void)hipHostFree(ks->h_up);
-    if (ks->d_keys) (void)hipFree(ks->d_keys);  // hipFree waits for outstanding work on the device
-    if (ks->d_eiv) (void)hipFree(ks->d_eiv);
+    // Round keys, E_k(IV) and the staged schedules are wiped before their memory goes back
+    // to the allocator.  (The creating engine may be gone, so not on its stream: wait for the
+    // device, as hipFree does anyway, then clear on the null stream.)
+    if (ks->h_up) {
+        memset(ks->h_up, 0, sizeof(DevKey) * (size_t)ks->cap_up);
+        (void)hipHostFree(ks->h_up);
+    }
+    const size_t slots = table_slots(ks);
+    if (ks->d_keys || ks->d_eiv) (void)hipDeviceSynchronize();
+    if (ks->d_keys) {
+        (void)hipMemset(ks->d_keys, 0, sizeof(DevKey) * slots);
+        (void)hipFree(ks->d_keys);  // hipFree waits for outstanding work on the device
+    }
+    if (ks->d_eiv) {
+        (void)hipMemset(ks->d_eiv, 0, sizeof(uint4) * slots);
+        (void)hipFree(ks->d_eiv);
+    }
     delete ks;
     return FPNN_AES_OK;
 }
@@ -1349,6 +1378,35 @@ int fpnn_aes_keyset_reserve(fpnn_aes_engine *e, uint32_t capacity, int nrounds, 
     return FPNN_AES_OK;
 }
 
+// Grow the table to at least `need` slots, keeping its contents (queued after everything
+// before it); new slots are as fpnn_aes_keyset_reserve leaves them.  The old table is zeroed
+// before it is freed.  Waits for the engine's stream when it grows; nothing otherwise.
+static int keyset_grow(fpnn_aes_keyset *ks, uint32_t need) {
+    const uint32_t have = table_slots(ks);
+    if (need <= have) return FPNN_AES_OK;
+    fpnn_aes_engine *e = ks->e;
+    uint32_t cap = have;
+    while (cap < need) cap = cap > 0x7fffffffu ? need : 2 * cap;
+    DevKey *nk = nullptr;
+    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&nk), sizeof(DevKey) * (size_t)cap));
+    HIP_TRY(hipMemsetAsync(nk + have, 0, sizeof(DevKey) * (size_t)(cap - have), e->stream));
+    HIP_TRY(hipMemcpyAsync(nk, ks->d_keys, sizeof(DevKey) * (size_t)have, hipMemcpyDeviceToDevice, e->stream));
+    uint4 *ne = nullptr;
+    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&ne), sizeof(uint4) * (size_t)cap));
+    HIP_TRY(hipMemcpyAsync(ne, ks->d_eiv, sizeof(uint4) * (size_t)have, hipMemcpyDeviceToDevice, e->stream));
+    HIP_TRY(launch_slot_eiv(nk, have, cap - have, ks->nrounds, t0le_of(e), ne, e->stream));
+    // the old table: wiped behind its last readers, freed once the stream has run dry
+    HIP_TRY(hipMemsetAsync(ks->d_keys, 0, sizeof(DevKey) * (size_t)have, e->stream));
+    HIP_TRY(hipMemsetAsync(ks->d_eiv, 0, sizeof(uint4) * (size_t)have, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));  // the old table may still be read by queued kernels
+    (void)hipFree(ks->d_keys);
+    (void)hipFree(ks->d_eiv);
+    ks->d_keys = nk;
+    ks->d_eiv = ne;
+    ks->capacity = cap;
+    return FPNN_AES_OK;
+}
+
 int fpnn_aes_keyset_set(fpnn_aes_keyset *ks, uint32_t first, uint32_t count, const fpnn_aes_schedule *ctx,
                         const uint8_t *ivs) {
     if (!ks || !ks->e || (count && !ctx) || !ks->up_done) return FPNN_AES_ERR_ARG;
@@ -1359,26 +1417,8 @@ int fpnn_aes_keyset_set(fpnn_aes_keyset *ks, uint32_t first, uint32_t count, con
     fpnn_aes_engine *e = ks->e;
     DeviceGuard g(ks->device);
     const uint32_t need = first + count;
-    if (need > ks->capacity) {  // grow, keeping the table (queued after everything before it)
-        uint32_t cap = ks->capacity;
-        while (cap < need) cap = cap > 0x7fffffffu ? need : 2 * cap;
-        DevKey *nk = nullptr;
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&nk), sizeof(DevKey) * (size_t)cap));
-        HIP_TRY(hipMemsetAsync(nk + ks->capacity, 0, sizeof(DevKey) * (size_t)(cap - ks->capacity), e->stream));
-        HIP_TRY(hipMemcpyAsync(nk, ks->d_keys, sizeof(DevKey) * (size_t)ks->capacity, hipMemcpyDeviceToDevice,
-                               e->stream));
-        uint4 *ne = nullptr;
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&ne), sizeof(uint4) * (size_t)cap));
-        HIP_TRY(hipMemcpyAsync(ne, ks->d_eiv, sizeof(uint4) * (size_t)ks->capacity, hipMemcpyDeviceToDevice,
-                               e->stream));
-        HIP_TRY(launch_slot_eiv(nk, ks->capacity, cap - ks->capacity, ks->nrounds, t0le_of(e), ne, e->stream));
-        HIP_TRY(hipStreamSynchronize(e->stream));  // the old table may still be read by queued kernels
-        (void)hipFree(ks->d_keys);
-        (void)hipFree(ks->d_eiv);
-        ks->d_keys = nk;
-        ks->d_eiv = ne;
-        ks->capacity = cap;
-    }
+    const int grc = keyset_grow(ks, need);
+    if (grc) return grc;
     if (ks->up_pending) {  // the staging still feeds the previous upload
         HIP_TRY(hipEventSynchronize(ks->up_done));
         ks->up_pending = false;
@@ -1421,6 +1461,88 @@ int fpnn_aes_keyset_get_schedule(fpnn_aes_keyset *ks, uint32_t slot, fpnn_aes_sc
     out->nrounds = (int)d.nrounds;
     for (int k = 0; k < 4 * ((int)d.nrounds + 1); k++) out->rk[k] = bswap32(d.rk[k]);
     return FPNN_AES_OK;
+}
+
+uint32_t fpnn_aes_keyset_capacity(const fpnn_aes_keyset *ks) { return ks ? table_slots(ks) : 0; }
+
+// ---- writes into a live table, on the device (k_keytable.hip) --------------------
+// The addressing part of a call: the host-known bound, the table grown to it (only then a
+// wait), the kernel's view of the table.
+static int keytable_args(fpnn_aes_keyset *ks, uint32_t first, uint32_t count, const uint32_t *slots,
+                         uint32_t slot_bound, KeyTableArgs &a) {
+    if (!slots && (uint64_t)first + count > 0xffffffffull) return FPNN_AES_ERR_RANGE;
+    if ((uintptr_t)slots & 3u) return FPNN_AES_ERR_ARG;
+    const uint32_t bound = slots ? slot_bound : first + count;
+    DeviceGuard g(ks->device);
+    const int rc = keyset_grow(ks, bound);
+    if (rc) return rc;
+    memset(&a, 0, sizeof a);
+    a.keys = ks->d_keys;
+    a.eiv = ks->d_eiv;
+    a.slots = slots;
+    a.first = first;
+    a.count = count;
+    a.slot_bound = bound;
+    a.t0le = t0le_of(ks->e);
+    a.fault = ks->e->d_fault;
+    return FPNN_AES_OK;
+}
+
+// Queue the write (set: k_set_keys, else k_clear_slots) on the table's engine.
+static int keytable_run(fpnn_aes_keyset *ks, KeyTableArgs &a, bool set) {
+    fpnn_aes_engine *e = ks->e;
+    DeviceGuard g(ks->device);
+    const BatchScope batch_scope(e);  // (an early return clears the pending flag)
+#ifdef FPNN_AES_BOUNDS
+    if (!e->d_aud) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->d_aud), sizeof(AuditTable)));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    AuditTable t;
+    memset(&t, 0, sizeof t);
+    auto ext = [&](AuditBuf i, const void *p, uint64_t bytes) {
+        if (!p) return;
+        t.lo[i] = (uint64_t)(uintptr_t)p;
+        t.hi[i] = t.lo[i] + bytes;
+    };
+    ext(AB_KEYS, a.keys, sizeof(DevKey) * (uint64_t)table_slots(ks));
+    ext(AB_EIV, a.eiv, 16 * (uint64_t)table_slots(ks));
+    ext(AB_KT_SLOTS, a.slots, 4 * (uint64_t)a.count);
+    ext(AB_KT_RAW, a.raw, (uint64_t)ks->keylen * a.count);
+    ext(AB_KT_IVS, a.ivs, 16 * (uint64_t)a.count);
+    ext(AB_KT_OK, a.ok, a.count);
+    HIP_TRY(hipMemcpy(e->d_aud, &t, sizeof t, hipMemcpyHostToDevice));
+    a.aud = e->d_aud;
+#endif
+    HIP_TRY(set ? launch_set_keys(a, ks->keylen, e->stream) : launch_clear_slots(a, ks->nrounds, e->stream));
+    batch_queued(e);
+    ks->count = std::max(ks->count, a.slot_bound);
+#ifdef FPNN_AES_BOUNDS
+    return audit_end(e, FPNN_AES_OK);
+#else
+    return FPNN_AES_OK;
+#endif
+}
+
+int fpnn_aes_keyset_set_keys(fpnn_aes_keyset *ks, uint32_t first, uint32_t count, const uint32_t *slots,
+                             uint32_t slot_bound, const uint8_t *keys, const uint8_t *ivs, const uint8_t *ok) {
+    if (!ks || !ks->e || (count && !keys)) return FPNN_AES_ERR_ARG;
+    if (count == 0) return FPNN_AES_OK;
+    KeyTableArgs a;
+    const int rc = keytable_args(ks, first, count, slots, slot_bound, a);
+    if (rc) return rc;
+    a.raw = keys;
+    a.ivs = ivs;
+    a.ok = ok;
+    return keytable_run(ks, a, true);
+}
+
+int fpnn_aes_keyset_clear(fpnn_aes_keyset *ks, uint32_t first, uint32_t count, const uint32_t *slots,
+                          uint32_t slot_bound) {
+    if (!ks || !ks->e) return FPNN_AES_ERR_ARG;
+    if (count == 0) return FPNN_AES_OK;
+    KeyTableArgs a;
+    const int rc = keytable_args(ks, first, count, slots, slot_bound, a);
+    if (rc) return rc;
+    return keytable_run(ks, a, false);
 }
 
 // ---- batches ---------------------------------------------------------------------
@@ -3331,6 +3453,15 @@ int ecdh_const(int curve, EccConst &c) {
 
 bool aligned4(const void *p) { return ((uintptr_t)p & 3u) == 0; }
 
+// d_ecdh held derived keys (or a private key): zero the bytes the call used, queued behind
+// their last reader on the engine's stream.
+int ecdh_wipe(fpnn_aes_engine *e, size_t bytes) {
+    if (!e->d_ecdh || !bytes) return FPNN_AES_OK;
+    DeviceGuard g(e->device);
+    HIP_TRY(hipMemsetAsync(e->d_ecdh, 0, std::min<uint64_t>(bytes, e->cap_ecdh), e->stream));
+    return FPNN_AES_OK;
+}
+
 int ecdh_launch(fpnn_aes_engine *e, int curve, const EccConst &c, const EcdhJob &j) {
     if (j.count == 0) return FPNN_AES_OK;
     if (!aligned4(j.priv) || !aligned4(j.pub) || !aligned4(j.key_out) || !aligned4(j.iv_out) ||
@@ -3466,7 +3597,38 @@ int fpnn_ecdh_keyset(fpnn_aes_engine *e, int curve, const uint8_t *private_key, 
     uint8_t *tmp = e->d_ecdh;
     rc = fpnn_ecdh_calc_keys(e, curve, private_key, peer_public, count, keylen, tmp, tmp + kb, ok ? ok : tmp + kb + ib);
     if (!rc) rc = fpnn_aes_keyset_create(e, count, (size_t)keylen, tmp, tmp + kb, 0, out);  // synchronizes
-    return rc;
+    const int wrc = ecdh_wipe(e, kb + ib + count);
+    return rc ? rc : wrc;
+}
+
+int fpnn_ecdh_accept(fpnn_aes_engine *e, int curve, const uint8_t *private_key, const uint8_t *peer_public,
+                     uint32_t count, fpnn_aes_keyset *ks, uint32_t first, const uint32_t *slots, uint32_t slot_bound,
+                     uint8_t *ok) {
+    if (!e || !private_key || !ks || ks->e != e || (count && !peer_public)) return FPNN_AES_ERR_ARG;
+    if (ks->keylen != 16 && ks->keylen != 32) return FPNN_AES_ERR_KEYLEN;
+    if (fpnn_ecdh_secret_len(curve) < 0) {
+        g_last_error = "unknown ECDH curve";
+        return FPNN_AES_ERR_ARG;
+    }
+    if (count == 0) return FPNN_AES_OK;
+    KeyTableArgs a;
+    int rc = keytable_args(ks, first, count, slots, slot_bound, a);  // (grows the table when the bound asks for it)
+    if (rc) return rc;
+    DeviceGuard g(e->device);
+    const int keylen = (int)ks->keylen;
+    const size_t kb = (size_t)count * keylen, ib = (size_t)count * 16;
+    rc = grow(e, e->d_ecdh, e->cap_ecdh, kb + ib + count);  // keys | ivs | ok, engine scratch
+    if (rc) return rc;
+    uint8_t *tmp = e->d_ecdh, *okp = ok ? ok : tmp + kb + ib;
+    rc = fpnn_ecdh_calc_keys(e, curve, private_key, peer_public, count, keylen, tmp, tmp + kb, okp);
+    if (!rc) {
+        a.raw = tmp;
+        a.ivs = tmp + kb;
+        a.ok = okp;
+        rc = keytable_run(ks, a, true);
+    }
+    const int wrc = ecdh_wipe(e, kb + ib + count);  // behind k_set_keys, the scratch's last reader
+    return rc ? rc : wrc;
 }
 
 int fpnn_ecdh_calc_keys_host(fpnn_aes_engine *e, int curve, const uint8_t *private_key, const uint8_t *peer_public,
@@ -3493,7 +3655,8 @@ int fpnn_ecdh_calc_keys_host(fpnn_aes_engine *e, int curve, const uint8_t *priva
         if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
         if (err != hipSuccess) { rc = hip_fail(err, "ecdh download"); break; }
     } while (0);
-    return rc;
+    const int wrc = ecdh_wipe(e, pb + kb + ib + count);
+    return rc ? rc : wrc;
 }
 
 int fpnn_ecdh_calc_key_host(fpnn_aes_engine *e, const char *curve, const uint8_t *private_key, size_t private_len,
@@ -3518,7 +3681,8 @@ int fpnn_ecdh_calc_key_host(fpnn_aes_engine *e, const char *curve, const uint8_t
         if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
         if (err != hipSuccess) { rc = hip_fail(err, "ecdh download"); break; }
     } while (0);
-    if (rc) return rc;
+    const int wrc = ecdh_wipe(e, 64 + 32 + 16 + 16);
+    if (rc || wrc) return rc ? rc : wrc;
     if (!res[48]) return 0;
     memcpy(key, res, (size_t)keylen);
     memcpy(iv, res + 32, 16);
@@ -3543,7 +3707,8 @@ int fpnn_ecdh_public_key_host(fpnn_aes_engine *e, int curve, const uint8_t *priv
         if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
         if (err != hipSuccess) { rc = hip_fail(err, "ecdh download"); break; }
     } while (0);
-    if (rc) return rc;
+    const int wrc = ecdh_wipe(e, 32 + 64 + 16);  // (the private key went through it)
+    if (rc || wrc) return rc ? rc : wrc;
     memcpy(public_key, res, (size_t)(2 * sl));
     return res[64] ? 1 : 0;
 }

@@ -296,6 +296,27 @@ hipError_t launch_slot_eiv(const DevKey *keys, uint32_t first, uint32_t count, i
                            uint4 *eiv, hipStream_t st);
 hipError_t launch_expand_keys(const uint8_t *keys, uint32_t keylen, const uint8_t *ivs, uint32_t count,
                               const uint8_t *sbox, DevKey *out, hipStream_t st);
+// Writes into a live key table (k_keytable.hip; fpnn_aes_keyset_set_keys / _clear,
+// fpnn_ecdh_accept).  Entry i < count goes to slot s_i = slots ? slots[i] : first + i; an
+// entry with s_i >= slot_bound writes nothing and ORs kFaultKeySlot into *fault (the caller
+// passes slot_bound <= the table's allocated slots; first + count when slots is null).
+constexpr uint32_t kFaultKeySlot = 8u;  // a slots[] entry at or past the call's slot_bound
+struct KeyTableArgs {
+    DevKey *keys;
+    uint4 *eiv;
+    const uint32_t *slots;  // or null
+    uint32_t first, count, slot_bound, pad;
+    const uint8_t *raw;   // set_keys: count raw keys of the table's key length
+    const uint8_t *ivs;   // set_keys: count * 16 bytes, or null (zero IVs)
+    const uint8_t *ok;    // set_keys: entries with ok[i] == 0 write nothing; or null
+    const uint32_t *t0le;
+    uint32_t *fault;
+    AuditTable *aud;      // the address-audit build's extent table (null in the product build)
+};
+// one lane per entry: the expanded DevKey and eiv[s_i] = E_k(IV) of the slot, in one launch
+hipError_t launch_set_keys(const KeyTableArgs &a, uint32_t keylen, hipStream_t st);
+// the slot as fpnn_aes_keyset_reserve leaves it: a zero DevKey and launch_slot_eiv's value for one
+hipError_t launch_clear_slots(const KeyTableArgs &a, int nrounds, hipStream_t st);
 // Host-mapped frame moves: a job copies n segments, segment i from address sbase + soff[i]
 // to dbase + doff[i], len[i] + extra bytes (soff/doff/len device arrays; either side may be
 // mapped host memory; a base of 0 makes the offsets absolute device-visible addresses).

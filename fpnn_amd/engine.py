@@ -318,6 +318,26 @@ class Engine:
                                    C.byref(h)), "ecdh_keyset")
         return KeySet.adopt(self, h, n, keylen), ok
 
+    def ecdh_accept(self, curve: str, private_key: bytes, peer_public: torch.Tensor, keys: "KeySet", *,
+                    first: int = 0, slots: Optional[torch.Tensor] = None, slot_bound: Optional[int] = None,
+                    ok: Optional[torch.Tensor] = None, count: Optional[int] = None):
+        """fpnn_ecdh_accept: derive every peer's (key, iv) with the table's key length and
+        write them into slot slots[i] / first + i of the live table `keys`; where the
+        derivation fails the slot keeps its contents.  Queued; returns the device ok array
+        (the one passed in, or a new one)."""
+        cv = self.ecdh_curve(curve)
+        n = peer_public.numel() // (2 * lib.fpnn_ecdh_secret_len(cv)) if count is None else count
+        if ok is None:
+            ok = torch.empty(max(n, 1), dtype=torch.uint8, device=peer_public.device)
+        elif ok.numel() < n:
+            raise ValueError(f"ok: {ok.numel()} entries for {n} peers")
+        sp, sb, bound = KeySet._addressing(n, first, slots, slot_bound)
+        check(lib.fpnn_ecdh_accept(self._h, cv, bytes(private_key), _ptr(peer_public), n, keys.handle, first, sp, sb,
+                                   _ptr(ok)), "ecdh_accept")
+        if n:
+            keys.count = max(keys.count, bound)
+        return ok
+
     def ecdh_calc_key_host(self, curve: str, private_key: bytes, peer_public: bytes, keylen: int):
         """One connection, exactly ECCKeyExchange::init + calcKey -> (ok, key, iv)."""
         key, iv = C.create_string_buffer(32), C.create_string_buffer(16)
@@ -462,6 +482,51 @@ class KeySet:
         ib = b"".join(bytes(v) for v in ivs) if ivs is not None else None
         check(lib.fpnn_aes_keyset_set(self._h, first, n, ctx, C.c_char_p(ib) if ib is not None else None), "keyset_set")
         self.count = max(self.count, first + n)
+
+    # -- writes into a live table, on the device (queued on the creating engine's stream) -----
+    @property
+    def capacity(self) -> int:
+        """Slots the table's allocations hold (fpnn_aes_keyset_capacity)."""
+        return lib.fpnn_aes_keyset_capacity(self._h)
+
+    @staticmethod
+    def _addressing(count, first, slots, slot_bound):
+        """(slots pointer, slot_bound argument, host-known bound) of a set_keys / clear /
+        ecdh_accept call: first + count without slots, slot_bound with them."""
+        if slots is None:
+            return None, 0, first + count
+        if slots.dtype not in (torch.int32, torch.uint32):
+            raise TypeError(f"slots: dtype {slots.dtype}, expected {torch.int32}")
+        if slots.numel() < count:
+            raise ValueError(f"slots: {slots.numel()} entries for {count} keys")
+        if slot_bound is None:
+            raise ValueError("slot_bound is required with slots (no slot index at or above it is written)")
+        return _ptr(slots), slot_bound, slot_bound
+
+    def set_keys(self, keys: torch.Tensor, ivs: Optional[torch.Tensor] = None, *, first: int = 0,
+                 slots: Optional[torch.Tensor] = None, slot_bound: Optional[int] = None,
+                 ok: Optional[torch.Tensor] = None, count: Optional[int] = None):
+        """fpnn_aes_keyset_set_keys: raw keys (device uint8, count * keylen) and IVs (device
+        uint8, count * 16, None => zero) expanded on the device into slot slots[i] (device
+        int32) or first + i; entries with ok[i] == 0 (device uint8) are left alone."""
+        n = keys.numel() // self.keylen if count is None else count
+        if keys.numel() < n * self.keylen or (ivs is not None and ivs.numel() < 16 * n) or \
+                (ok is not None and ok.numel() < n):
+            raise ValueError(f"keys / ivs / ok too short for {n} entries")
+        sp, sb, bound = self._addressing(n, first, slots, slot_bound)
+        check(lib.fpnn_aes_keyset_set_keys(self._h, first, n, sp, sb, _ptr(keys), _ptr(ivs), _ptr(ok)),
+              "keyset_set_keys")
+        if n:
+            self.count = max(self.count, bound)
+
+    def clear(self, first: int = 0, count: Optional[int] = None, *, slots: Optional[torch.Tensor] = None,
+              slot_bound: Optional[int] = None):
+        """fpnn_aes_keyset_clear: the slots become what a never-set slot of reserve() holds."""
+        n = (slots.numel() if slots is not None else 0) if count is None else count
+        sp, sb, bound = self._addressing(n, first, slots, slot_bound)
+        check(lib.fpnn_aes_keyset_clear(self._h, first, n, sp, sb), "keyset_clear")
+        if n:
+            self.count = max(self.count, bound)
 
     @classmethod
     def adopt(cls, engine: Engine, h, count: int, keylen: int) -> "KeySet":

@@ -89,7 +89,8 @@ void *fpnn_aes_engine_stream(fpnn_aes_engine *e);
  * device arrays, because every piece of cross-call scratch state (the block map's
  * look-back epoch and tickets, the length-order block and K2h's tickets) is reset on the
  * device by the kernels that use it (tests/test_gpu_graph.py).  The *_frames stream calls'
- * per-segment scratch is sized from max_segments as well. */
+ * per-segment scratch is sized from max_segments as well, and so is the scratch of
+ * fpnn_ecdh_accept (fpnn_ecdh.h) for up to max_segments peers per call. */
 int fpnn_aes_engine_reserve(fpnn_aes_engine *e, uint64_t max_segments, uint64_t max_blocks);
 
 /* Placement of the engines behind the C++ classes (Encryptor, EncryptorBatch,
@@ -131,6 +132,41 @@ int fpnn_aes_keyset_destroy(fpnn_aes_keyset *ks);
 int fpnn_aes_keyset_nrounds(const fpnn_aes_keyset *ks);
 /* Copy the expanded schedule of slot i back to the host (rijndael_context layout). */
 int fpnn_aes_keyset_get_schedule(fpnn_aes_keyset *ks, uint32_t slot, fpnn_aes_schedule *out);
+
+/* ---- accept and retire connections in a LIVE table, on the device ------------- */
+/* Slots the table's allocations hold: the reserved (or grown) capacity; for a key set made
+ * by _create / _from_schedules, its count until a call below grows it.  0 for NULL. */
+uint32_t fpnn_aes_keyset_capacity(const fpnn_aes_keyset *ks);
+/* fpnn_aes_keyset_set_keys: `count` RAW keys of the table's key length (keys: DEVICE,
+ * count * keylen bytes, any alignment) and their IVs (ivs: DEVICE, count * 16 bytes, or
+ * NULL => zero IVs) are expanded on the device (rijndael_setup_encrypt's schedule,
+ * base/rijndael.c:712-799) and written, with the slot's first keystream block, into
+ *     slot s_i = slots ? slots[i] : first + i        (slots: DEVICE, 4-byte aligned, or NULL)
+ * An entry with ok != NULL and ok[i] == 0 (ok: DEVICE, count bytes) writes nothing: the slot
+ * keeps what it held.
+ * fpnn_aes_keyset_clear: the named slots become bit for bit what a never-set slot of
+ * fpnn_aes_keyset_reserve holds (a closed connection's key stops existing).
+ *
+ * Both work on any key set and are QUEUED on the stream of the engine that made the key
+ * set, like a batch call: batches queued before the call see the old slots, batches queued
+ * after it the new ones; no key byte passes through host memory.
+ *
+ * The bound known to the host is first + count when slots is NULL and slot_bound otherwise
+ * (slot_bound is not used when slots is NULL).  When it exceeds fpnn_aes_keyset_capacity the
+ * table grows exactly as fpnn_aes_keyset_set grows it (contents kept; that waits for the
+ * stream once); otherwise the call allocates nothing and waits for nothing.  The key set's
+ * count becomes max(count, bound).  slot_bound may be below the capacity; the kernels
+ * check against slot_bound: an entry with slots[i] >= slot_bound writes nothing, the other
+ * entries of the call are written, and the next fpnn_aes_engine_sync returns
+ * FPNN_AES_ERR_DEVICE (once; the engine stays usable).  Naming one slot twice in one call is
+ * the caller's error: which entry the slot ends up with is not defined.
+ * FPNN_AES_ERR_ARG: ks NULL, keys NULL with count != 0, slots not 4-byte aligned;
+ * FPNN_AES_ERR_RANGE: first + count past 2^32 - 1.  count == 0 is FPNN_AES_OK and a no-op. */
+int fpnn_aes_keyset_set_keys(fpnn_aes_keyset *ks, uint32_t first, uint32_t count,
+        const uint32_t *slots, uint32_t slot_bound,      /* dev or NULL; bound used only with slots */
+        const uint8_t *keys, const uint8_t *ivs, const uint8_t *ok);   /* all dev; ivs, ok may be NULL */
+int fpnn_aes_keyset_clear(fpnn_aes_keyset *ks, uint32_t first, uint32_t count,
+        const uint32_t *slots, uint32_t slot_bound);
 
 /* ---- batch descriptor ---------------------------------------------------------- */
 /* A batch is `count` independent segments.  Segment i reads len_i bytes at

@@ -75,9 +75,30 @@ int fpnn_ecdh_public_keys(fpnn_aes_engine *e, int curve, const uint8_t *private_
  * (the kernel writes it; a host pointer here is a GPU memory fault).  Slot i is
  * connection i; where ok[i] == 0 the slot holds the zero-derived key and must not be
  * used (the reference refuses the connection).  Synchronous (returns a usable key set);
- * the derived keys pass through the engine's own scratch, which is kept between calls. */
+ * the derived keys pass through the engine's own scratch, which the call zeroes again
+ * (queued behind the expansion that read it), as every call of this header does with the
+ * scratch bytes it used. */
 int fpnn_ecdh_keyset(fpnn_aes_engine *e, int curve, const uint8_t *private_key, const uint8_t *peer_public,
                      uint32_t count, int keylen, uint8_t *ok, fpnn_aes_keyset **out);
+
+/* Accept a batch of connections into a LIVE key table: derive (key, iv) for `count` peers
+ * with the table's key length (16 or 32; a 24-byte table is FPNN_AES_ERR_KEYLEN), expand
+ * each on the device and write it into
+ *     slot s_i = slots ? slots[i] : first + i
+ * of ks, exactly as fpnn_aes_keyset_set_keys (fpnn_aes.h) addresses, bounds (slot_bound,
+ * FPNN_AES_ERR_DEVICE at the next sync for an entry at or past it) and grows the table.
+ * Where ok[i] == 0 -- the reference refuses the connection -- the slot keeps its previous
+ * contents.  private_key: host; peer_public: DEVICE, count * 2*secret_len bytes; slots:
+ * DEVICE or NULL; ok: DEVICE, count bytes, or NULL.  ks must have been made on e.
+ * Queued on the engine stream: the ECDH kernel writes the keys into engine scratch, the
+ * table write reads them from there, and the scratch is zeroed behind it; batches queued
+ * after the call cipher under the new keys with no host wait in between, and no key byte
+ * reaches host memory.  After fpnn_aes_engine_reserve with max_segments >= count (and a
+ * table that holds the bound) the call allocates nothing and may be captured in a graph.
+ * Naming one slot twice in one call is the caller's error. */
+int fpnn_ecdh_accept(fpnn_aes_engine *e, int curve, const uint8_t *private_key /*host*/,
+        const uint8_t *peer_public /*dev*/, uint32_t count, fpnn_aes_keyset *ks,
+        uint32_t first, const uint32_t *slots, uint32_t slot_bound, uint8_t *ok /*dev or NULL*/);
 
 /* fpnn_ecdh_calc_keys with host buffers (peer_public count * 2*secret_len, keys, ivs,
  * ok); synchronous. */

@@ -7,6 +7,11 @@ cores, one process per core.
 
   python tools/bench_ecdh.py [--n 65536] [--reps 5] [--cpu-seconds 3]
 Prints one JSON object (derivations/s per curve).
+
+  python tools/bench_ecdh.py --accept [--n 65536] [--reps 7]
+The "accept" row instead (accept_row below): the time from queueing the ECDH of n peers to
+the end of the first package encrypt under their keys, through the host (calc_keys, copy
+back, host key expansion, fpnn_aes_keyset_set) and on the device (fpnn_ecdh_accept).
 """
 from __future__ import annotations
 
@@ -73,6 +78,100 @@ def gpu_percall(engine, curve: str, calls: int):
     return statistics.median(times) * 1e6
 
 
+def accept_row(engine, n: int, reps: int):
+    """The "accept" row: n secp256k1 peers into a reserved AES-256 table, from the queue of
+    the ECDH to the completion of a following 145-byte package encrypt that names every new
+    slot, by two routes measured alternately in this one session (host clock around work that
+    ends in a device synchronise):
+      host    fpnn_ecdh_calc_keys -> device-to-host copy of (key, iv) -> one host
+              fpnn_aes_setup_encrypt per connection -> fpnn_aes_keyset_set -> encrypt
+      device  fpnn_ecdh_accept -> encrypt
+    The host expansion is a Python loop over a ctypes call; the same loop over a C call that
+    does nothing (fpnn_aes_keyset_nrounds(NULL)) is timed beside it and subtracted, so
+    host_ms is the route less the interpreter's share (host_wall_ms keeps it)."""
+    import ctypes as C
+    import statistics
+    import numpy as np
+    import torch
+    import fpnn_amd
+    from fpnn_amd._lib import Schedule
+    lib = fpnn_amd.lib
+    curve, keylen, L = "secp256k1", 32, 145
+    rng = np.random.default_rng(n + 1)
+    privs = torch.from_numpy(rng.integers(0, 256, (n, 32), dtype=np.uint8)).to("cuda:0")
+    privs[:, 0] &= 0x7F
+    peers, _ = engine.ecdh_public_keys(curve, privs)  # setup, not timed
+    server = bytes(rng.integers(1, 255, 32, dtype=np.uint8))
+    cv = engine.ecdh_curve(curve)
+    engine.reserve(n, n * ((L + 15) // 16))
+    tables = {r: fpnn_amd.KeySet.reserve(engine, n, keylen) for r in ("host", "device")}
+    src = torch.from_numpy(rng.integers(0, 256, n * L, dtype=np.uint8)).to("cuda:0")
+    dst = {r: torch.zeros(n * L, dtype=torch.uint8, device="cuda:0") for r in tables}
+    slot = torch.arange(n, dtype=torch.int32, device="cuda:0")
+    keys = torch.empty((n, keylen), dtype=torch.uint8, device="cuda:0")
+    ivs = torch.empty((n, 16), dtype=torch.uint8, device="cuda:0")
+    ok = torch.empty(n, dtype=torch.uint8, device="cuda:0")
+    ctx = (Schedule * n)()
+    ptr = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+    u8p = C.POINTER(C.c_uint8)
+
+    def encrypt(route):
+        engine.package_encrypt(src, dst[route], n, tables[route], stride=L, uniform_len=L, key_slot=slot, max_len=L)
+
+    def host_route():
+        t0 = time.perf_counter()
+        fpnn_amd.check(lib.fpnn_ecdh_calc_keys(engine.handle, cv, server, ptr(peers), n, keylen, ptr(keys), ptr(ivs),
+                                               ptr(ok)), "calc_keys")
+        hk, hi = keys.cpu().numpy(), ivs.cpu().numpy()  # (waits for the derivation)
+        t1 = time.perf_counter()
+        kp = hk.ctypes.data
+        for i in range(n):
+            lib.fpnn_aes_setup_encrypt(C.byref(ctx[i]), C.cast(kp + keylen * i, u8p), keylen)
+        t2 = time.perf_counter()
+        for i in range(n):  # the loop's own cost: the same argument work around a call that does nothing
+            C.byref(ctx[i])
+            C.cast(kp + keylen * i, u8p)
+            lib.fpnn_aes_keyset_nrounds(None)
+        t3 = time.perf_counter()
+        fpnn_amd.check(lib.fpnn_aes_keyset_set(tables["host"].handle, 0, n, ctx, hi.ctypes.data_as(C.c_void_p)),
+                       "keyset_set")
+        tables["host"].count = n
+        encrypt("host")
+        torch.cuda.synchronize()
+        t4 = time.perf_counter()
+        wall = t4 - t0 - (t3 - t2)  # the route as it ran (the do-nothing loop is no part of it)
+        return wall - (t3 - t2), wall, (t1 - t0, (t2 - t1) - (t3 - t2), t4 - t3)  # less the interpreter's share
+
+    def device_route():
+        t0 = time.perf_counter()
+        engine.ecdh_accept(curve, server, peers, tables["device"], ok=ok, count=n)
+        encrypt("device")
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+
+    for _ in range(2):  # warm-up: code objects, scratch and tables at their final size
+        host_route()
+        device_route()
+    assert torch.equal(dst["host"], dst["device"]) and bool(ok.all())
+    host, wall, dev, parts = [], [], [], []
+    for _ in range(reps):  # alternating
+        h, w, p = host_route()
+        host.append(h)
+        wall.append(w)
+        parts.append(p)
+        dev.append(device_route())
+    ms = lambda v: round(statistics.median(v) * 1e3, 3)  # noqa: E731
+    for t in tables.values():
+        t.close()
+    return {"n": n, "reps": reps, "frame_bytes": L,
+            "host_ms": ms(host), "host_ms_min": round(min(host) * 1e3, 3), "host_wall_ms": ms(wall),
+            "host_parts_ms": {"derive_and_copy_back": ms([p[0] for p in parts]),
+                              "host_expansion": ms([p[1] for p in parts]),
+                              "upload_and_encrypt": ms([p[2] for p in parts])},
+            "device_ms": ms(dev), "device_ms_min": round(min(dev) * 1e3, 3),
+            "host_over_device": round(statistics.median(host) / statistics.median(dev), 2)}
+
+
 def cpu_rate(curve: str, procs: int, seconds: float):
     """calcKey/s of the reference, `procs` processes in parallel (one per core)."""
     g = json.load(open(os.path.join(ROOT, "tests", "golden", "ecdh_cases.json")))
@@ -102,9 +201,15 @@ def main():
     ap.add_argument("--curves", default="secp256k1,secp256r1,secp224r1,secp192r1")
     ap.add_argument("--no-cpu", action="store_true", help="skip the reference CPU legs (profiling runs)")
     ap.add_argument("--percall", type=int, default=0, help="also time this many single-peer calcKey calls")
+    ap.add_argument("--accept", action="store_true",
+                    help="only the accept row: ECDH -> live key table -> first encrypt, host route against device route")
     args = ap.parse_args()
     import fpnn_amd
     eng = fpnn_amd.Engine(0)
+    if args.accept:
+        print(json.dumps({"metric": "accept: ECDH queued -> 145-B package encrypt of every new slot done (ms)",
+                          "accept": accept_row(eng, args.n, max(args.reps, 7))}))
+        return
     cores = len(os.sched_getaffinity(0))
     try:
         quota = open("/sys/fs/cgroup/cpu.max").read().split()
