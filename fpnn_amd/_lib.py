@@ -113,12 +113,18 @@ SIGNATURES = {
     "fpnn_aes_keyset_capacity": (C.c_uint32, [_vp]),
     "fpnn_aes_keyset_set_keys": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _vp, C.c_uint32, _vp, _vp, _vp]),
     "fpnn_aes_keyset_clear": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _vp, C.c_uint32]),
+    "fpnn_aes_stream_open": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _vp, C.c_uint32, _vp, _vp, _vp]),
+    "fpnn_aes_stream_close": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _vp, C.c_uint32, _vp, _vp]),
     "fpnn_aes_package_encrypt": (C.c_int, [_vp, C.POINTER(BatchDesc)]),
     "fpnn_aes_package_decrypt": (C.c_int, [_vp, C.POINTER(BatchDesc)]),
     "fpnn_aes_stream_encrypt": (C.c_int, [_vp, C.POINTER(BatchDesc), _vp, _vp]),
     "fpnn_aes_stream_decrypt": (C.c_int, [_vp, C.POINTER(BatchDesc), _vp, _vp]),
     "fpnn_aes_stream_encrypt_frames": (C.c_int, [_vp, C.POINTER(BatchDesc), _vp, C.c_uint32, _vp, _vp]),
     "fpnn_aes_stream_decrypt_frames": (C.c_int, [_vp, C.POINTER(BatchDesc), _vp, C.c_uint32, _vp, _vp]),
+    "fpnn_aes_stream_encrypt_frames_at": (C.c_int, [_vp, C.POINTER(BatchDesc), _vp, C.c_uint32, _vp, C.c_uint32, _vp,
+                                                    _vp]),
+    "fpnn_aes_stream_decrypt_frames_at": (C.c_int, [_vp, C.POINTER(BatchDesc), _vp, C.c_uint32, _vp, C.c_uint32, _vp,
+                                                    _vp]),
     "fpnn_aes_cfb_host": (C.c_int, [_vp, C.POINTER(Schedule), C.c_int, _vp, _vp, C.c_size_t, _u8p,
                                     C.POINTER(C.c_size_t)]),
     "fpnn_aes_package_host": (C.c_int, [_vp, C.c_int, C.POINTER(HostFrame), C.c_uint32, _vp, C.c_uint32]),
@@ -133,6 +139,8 @@ SIGNATURES = {
     "fpnn_aes_package_recv": (C.c_int, [_vp, C.POINTER(BatchDesc), C.c_uint32, C.c_uint32, _vp, _vp, _vp]),
     "fpnn_aes_stream_recv": (C.c_int, [_vp, C.POINTER(BatchDesc), _vp, _vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp,
                                        _vp]),
+    "fpnn_aes_stream_recv_at": (C.c_int, [_vp, C.POINTER(BatchDesc), _vp, C.c_uint32, _vp, _vp, _vp, C.c_uint32,
+                                          C.c_uint32, _vp, _vp, _vp]),
     "fpnn_aes_fill_synthetic": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, C.c_uint64]),
     "fpnn_aes_engine_set_timing": (C.c_int, [_vp, C.c_int]),
     "fpnn_aes_engine_kernel_stats": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),

@@ -3,8 +3,8 @@
 //
 // Every global load and store of K2h (k_hybrid.hip), K2's ragged path (k_encrypt.hip), the
 // length-order kernels (k_support.hip), the many-frames-per-stream kernels
-// (k_stream_frames.hip: the caller's arrays and the payload) and the key-table writes
-// (k_keytable.hip: the caller's arrays, the DevKey slots and eiv[]) names the buffer it
+// (k_stream_frames.hip: the caller's arrays and the payload) and the key-table kernels
+// (k_keytable.hip: the caller's arrays, the DevKey slots, eiv[] and the stream state) names the buffer it
 // indexes through FA_AT / FA_SEG / FA_RG.  In the audit build each one checks its byte range against an extent:
 //   * the array extents the host supplies per call (AuditTable::lo/hi: descriptor arrays of
 //     `count` entries, the key set's slots, perm[] of `count` entries, the wave sinks, the
@@ -45,6 +45,9 @@ enum AuditBuf : uint32_t {
     AB_KT_RAW,
     AB_KT_IVS,
     AB_KT_OK,
+    AB_STATE_SLOT,  // slot-addressed stream calls: state_slot[], nstreams entries (the state arrays
+                    // then hold slot_bound entries)
+    AB_SEG_SLOT,    // their decrypt: the per-segment key slots the walk writes, `count` entries
     kAuditBufs
 };
 

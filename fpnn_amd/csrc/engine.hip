@@ -279,6 +279,8 @@ struct fpnn_aes_engine {
     uint64_t cap_sf_iv = 0;
     uint32_t *d_sf_pos = nullptr;
     uint64_t cap_sf_pos = 0;
+    uint32_t *d_sf_slot = nullptr;  // the slot-addressed (_at) decrypt: every segment's key slot
+    uint64_t cap_sf_slot = 0;
     uint64_t *d_lookback = nullptr;  // one-pass block map: tickets, epoch, tile status (zeroed when grown)
     uint64_t cap_lookback = 0;
     // device-side consistency checks (kFault*): a pinned word kernels may set, read when the
@@ -512,7 +514,8 @@ bool is_uniform_layout(const fpnn_aes_batch *b) {
 // engine's table (synchronous; the audit build is a checker, not a product).  The scratch
 // the call grows is grown here first so that its extent is known.
 // frames: a *_frames call -- first_frame[] is registered and the state arrays hold one entry
-// per stream.
+// per stream; with state_slot (the _at calls) slot_bound entries, and state_slot[] and the
+// per-segment slot scratch are registered (the latter also as key_slot: K1r's view of it).
 int audit_begin(fpnn_aes_engine *e, const fpnn_aes_batch *b, const uint8_t *iv_state, const uint32_t *pos_state,
                 KBatch &k, const FrameTable *frames = nullptr) {
     int rc;
@@ -539,11 +542,16 @@ int audit_begin(fpnn_aes_engine *e, const fpnn_aes_batch *b, const uint8_t *iv_s
     const uint64_t slots = std::max<uint64_t>(b->keys->count, b->keys->capacity);
     set(AB_KEYS, b->keys->d_keys, sizeof(DevKey) * slots);
     set(AB_EIV, b->keys->d_eiv, 16 * slots);
-    const uint64_t nstate = frames ? frames->nstreams : n;
+    const uint64_t nstate = !frames ? n : frames->state_slot ? frames->slot_bound : frames->nstreams;
     set(AB_IV_STATE, iv_state, 16 * nstate);
     set(AB_POS_STATE, pos_state, 4 * nstate);
     set(AB_POS_SNAP, pos_state, 4 * nstate);
     if (frames) set(AB_FIRST_FRAME, frames->first_frame, 4 * ((uint64_t)frames->nstreams + 1));
+    if (frames && frames->state_slot) {
+        set(AB_STATE_SLOT, frames->state_slot, 4 * (uint64_t)frames->nstreams);
+        set(AB_SEG_SLOT, frames->seg_slot, 4 * n);
+        set(AB_SLOT, frames->seg_slot, 4 * n);
+    }
     set(AB_PERM, e->d_perm, 4 * n);
     set(AB_SINK, e->d_sink, 16 * e->cap_sink);
     set(AB_BLOCK, e->d_buckets, 4 * (uint64_t)kLengthOrderWords);
@@ -585,7 +593,8 @@ const char *audit_buf_name(uint32_t i) {
     static const char *const names[kAuditBufs] = {"in", "out", "in_off", "out_off", "len", "key_slot", "keys", "eiv",
                                                   "iv_state", "pos_state", "perm", "sink", "length-order block",
                                                   "pos_snap", "in (outside its segment)", "out (outside its segment)",
-                                                  "first_frame", "slots", "raw keys", "ivs", "ok"};
+                                                  "first_frame", "slots", "raw keys", "ivs", "ok", "state_slot",
+                                                  "segment slots"};
     return i < kAuditBufs ? names[i] : "?";
 }
 
@@ -842,32 +851,57 @@ int run_decrypt(fpnn_aes_engine *e, const fpnn_aes_batch *b, uint8_t *iv_state, 
 
 // ---- many frames per stream in one call (fpnn_aes_stream_*_frames, k_stream_frames.hip) ----
 
+// The slot addressing of an _at call (fpnn_aes_stream_*_frames_at, fpnn_aes_stream_recv_at):
+// stream j's state AND key at state_slot[j], checked against slot_bound on the device.
+// one_frame: recv_at -- no first_frame, stream j is segment j.
+struct SlotAddr {
+    const uint32_t *state_slot;
+    uint32_t slot_bound;
+    bool one_frame;
+};
+
 int check_frames(const fpnn_aes_engine *e, const fpnn_aes_batch *b, const uint32_t *first_frame, uint32_t nstreams,
-                 const uint8_t *iv_state, const uint32_t *pos_state) {
+                 const uint8_t *iv_state, const uint32_t *pos_state, const SlotAddr *at) {
     const int rc = check_batch(e, b);
     if (rc) return rc;
     if (b->flags & FPNN_AES_F_WIRE_PREFIX) return FPNN_AES_ERR_ARG;
-    if (nstreams && (!first_frame || !iv_state || !pos_state || ((uintptr_t)iv_state & 15) ||
+    const bool need_first = !(at && at->one_frame);
+    if (nstreams && ((need_first && !first_frame) || !iv_state || !pos_state || ((uintptr_t)iv_state & 15) ||
                      ((uintptr_t)pos_state & 3) || ((uintptr_t)first_frame & 3)))
         return FPNN_AES_ERR_ARG;
+    if (at) {
+        // the slot names key and state: no second key addressing; the bound never grows the table
+        if (b->key_slot || ((uintptr_t)at->state_slot & 3) || (nstreams && !at->state_slot)) return FPNN_AES_ERR_ARG;
+        if (at->slot_bound > table_slots(b->keys)) return FPNN_AES_ERR_ARG;
+    }
     return FPNN_AES_OK;
+}
+
+FrameTable frame_table(fpnn_aes_engine *e, const uint32_t *first_frame, uint32_t nstreams, const SlotAddr *at) {
+    FrameTable f{first_frame, nstreams, 0u, e->d_fault, nullptr, nullptr};
+    if (at) {
+        f.state_slot = at->state_slot;
+        f.slot_bound = at->slot_bound;
+    }
+    return f;
 }
 
 // Encrypt: K2f, one quad per stream, sized as K2c is (by quads needed, at most one workgroup
 // per CU; further streams grid-stride).  Streams are visited in index order: no length order.
 int run_encrypt_frames_calls(fpnn_aes_engine *e, const fpnn_aes_batch *b, const uint32_t *first_frame,
-                             uint32_t nstreams, uint8_t *iv_state, uint32_t *pos_state) {
-    int rc = check_frames(e, b, first_frame, nstreams, iv_state, pos_state);
+                             uint32_t nstreams, uint8_t *iv_state, uint32_t *pos_state, const SlotAddr *at) {
+    int rc = check_frames(e, b, first_frame, nstreams, iv_state, pos_state, at);
     if (rc) return rc;
     if (!nstreams || !b->count) return FPNN_AES_OK;
     DeviceGuard g(e->device);
     const BatchScope batch_scope(e);  // (an early return clears the pending flag)
     KBatch k = make_kbatch(e, b, iv_state, pos_state);
-    const FrameTable f{first_frame, nstreams, 0u, e->d_fault};
+    const FrameTable f = frame_table(e, first_frame, nstreams, at);
 #ifdef FPNN_AES_BOUNDS
     if ((rc = audit_begin(e, b, iv_state, pos_state, k, &f))) return rc;
 #endif
-    const KeyMode km = (b->key_slot && b->keys->count > 1) ? KEY_LANE : KEY_UNIFORM;
+    // (an _at call: every stream's key from its slot of the table, whatever the table's size)
+    const KeyMode km = (at || (b->key_slot && b->keys->count > 1)) ? KEY_LANE : KEY_UNIFORM;
     const uint64_t lanes = 4ull * nstreams;
     int threads = 64;
     while (threads < kThreads && (uint64_t)threads * e->num_cus < lanes) threads *= 2;
@@ -884,8 +918,8 @@ int run_encrypt_frames_calls(fpnn_aes_engine *e, const fpnn_aes_batch *b, const 
 // gives every stream its last non-empty frame's.  The caller's state arrays are read by
 // the pre-pass and K1r's plan only through the snapshot, and written by the commit alone.
 int run_decrypt_frames_calls(fpnn_aes_engine *e, const fpnn_aes_batch *b, const uint32_t *first_frame,
-                             uint32_t nstreams, uint8_t *iv_state, uint32_t *pos_state) {
-    int rc = check_frames(e, b, first_frame, nstreams, iv_state, pos_state);
+                             uint32_t nstreams, uint8_t *iv_state, uint32_t *pos_state, const SlotAddr *at) {
+    int rc = check_frames(e, b, first_frame, nstreams, iv_state, pos_state, at);
     if (rc) return rc;
     if (!nstreams || !b->count) return FPNN_AES_OK;
     DeviceGuard g(e->device);
@@ -899,6 +933,7 @@ int run_decrypt_frames_calls(fpnn_aes_engine *e, const fpnn_aes_batch *b, const 
     if ((rc = grow(e, e->d_sf_prev, e->cap_sf_prev, n))) return rc;
     if ((rc = grow(e, e->d_sf_iv, e->cap_sf_iv, n))) return rc;
     if ((rc = grow(e, e->d_sf_pos, e->cap_sf_pos, n))) return rc;
+    if (at && (rc = grow(e, e->d_sf_slot, e->cap_sf_slot, n))) return rc;
     if ((rc = grow(e, e->d_bstart, e->cap_bstart, n + 1))) return rc;
     if ((rc = grow(e, e->d_plan, e->cap_plan, (uint64_t)grid * (kThreads / 64)))) return rc;
     if ((rc = grow(e, e->d_sink, e->cap_sink, 2ull * grid * (kThreads / 64)))) return rc;
@@ -910,11 +945,15 @@ int run_decrypt_frames_calls(fpnn_aes_engine *e, const fpnn_aes_batch *b, const 
         HIP_TRY(hipMemsetAsync(e->d_lookback, 0, e->cap_lookback * sizeof(uint64_t), e->stream));
     }
     KBatch k = make_kbatch(e, b, iv_state, pos_state);
-    const FrameTable f{first_frame, nstreams, 0u, e->d_fault};
+    FrameTable f = frame_table(e, first_frame, nstreams, at);
+    if (at) {  // the walk writes every segment's key slot; the pre-pass's second launch and K1r read it
+        f.seg_slot = e->d_sf_slot;
+        k.key_slot = e->d_sf_slot;
+    }
 #ifdef FPNN_AES_BOUNDS
     if ((rc = audit_begin(e, b, iv_state, pos_state, k, &f))) return rc;
 #endif
-    const KeyMode km = (b->key_slot && b->keys->count > 1) ? KEY_LANE : KEY_UNIFORM;
+    const KeyMode km = (at || (b->key_slot && b->keys->count > 1)) ? KEY_LANE : KEY_UNIFORM;
     // the pre-pass reads the ciphertext and the incoming state: before the block map (whose
     // block counts read pos_snap) and before any in-place write
     HIP_TRY(launch_stream_frames_state(k, f, b->keys->nrounds, km, e->d_snap_iv, e->d_snap_pos, e->d_sf_stream,
@@ -955,9 +994,9 @@ int run_decrypt_frames_calls(fpnn_aes_engine *e, const fpnn_aes_batch *b, const 
 }
 
 int run_frames(fpnn_aes_engine *e, const fpnn_aes_batch *b, const uint32_t *first_frame, uint32_t nstreams,
-               uint8_t *iv_state, uint32_t *pos_state, bool encrypt) {
-    const int rc = encrypt ? run_encrypt_frames_calls(e, b, first_frame, nstreams, iv_state, pos_state)
-                           : run_decrypt_frames_calls(e, b, first_frame, nstreams, iv_state, pos_state);
+               uint8_t *iv_state, uint32_t *pos_state, bool encrypt, const SlotAddr *at = nullptr) {
+    const int rc = encrypt ? run_encrypt_frames_calls(e, b, first_frame, nstreams, iv_state, pos_state, at)
+                           : run_decrypt_frames_calls(e, b, first_frame, nstreams, iv_state, pos_state, at);
 #ifdef FPNN_AES_BOUNDS
     return audit_end(e, rc);
 #else
@@ -983,7 +1022,8 @@ const char *fpnn_aes_version(void) {
            "batches, K2f quad per stream over many frames per call (stream_encrypt_frames; stream_decrypt_frames: "
            "state pre-pass + K1r); single calls <= 16 KiB: K0s resident server (K0 per launch); "
            "ECDH: one lane per derivation, special-prime folds as carry chains; "
-           "live key table: keyset_set_keys / keyset_clear / ecdh_accept, one lane per slot, queued)";
+           "live key table: keyset_set_keys / keyset_clear / ecdh_accept, one lane per slot, queued; "
+           "stream state by slot: stream_open / stream_close, stream_*_frames_at, stream_recv_at)";
 }
 
 int fpnn_aes_setup_encrypt(fpnn_aes_schedule *ctx, const uint8_t *key, size_t keylen) {
@@ -1108,7 +1148,7 @@ int fpnn_aes_engine_destroy(fpnn_aes_engine *e) {
                     (void *)e->d_fr_off, (void *)e->d_fr_slot, (void *)e->d_plan, (void *)e->d_sink,
                     (void *)e->d_desc_off, (void *)e->d_desc_len, (void *)e->d_ecdh, (void *)e->d_sstate,
                     (void *)e->d_lookback, (void *)e->d_sf_stream, (void *)e->d_sf_prev, (void *)e->d_sf_iv,
-                    (void *)e->d_sf_pos})
+                    (void *)e->d_sf_pos, (void *)e->d_sf_slot})
         release_scratch(e, p);
     if (e->stream) (void)hipStreamSynchronize(e->stream);
     free_deferred(e);
@@ -1230,6 +1270,7 @@ int fpnn_aes_engine_reserve(fpnn_aes_engine *e, uint64_t max_segments, uint64_t 
     if ((rc = grow(e, e->d_sf_prev, e->cap_sf_prev, max_segments))) return rc;
     if ((rc = grow(e, e->d_sf_iv, e->cap_sf_iv, max_segments))) return rc;
     if ((rc = grow(e, e->d_sf_pos, e->cap_sf_pos, max_segments))) return rc;
+    if ((rc = grow(e, e->d_sf_slot, e->cap_sf_slot, max_segments))) return rc;
     // fpnn_ecdh_accept of up to max_segments peers: key (<= 32) | iv (16) | ok (1) each
     if ((rc = grow(e, e->d_ecdh, e->cap_ecdh, max_segments * (32 + 16 + 1)))) return rc;
     return FPNN_AES_OK;
@@ -1545,6 +1586,69 @@ int fpnn_aes_keyset_clear(fpnn_aes_keyset *ks, uint32_t first, uint32_t count, c
     return keytable_run(ks, a, false);
 }
 
+// ---- stream state by slot (k_keytable.hip) ---------------------------------------
+// open: (IV of the slot, 0); close: all zero.  The table is read, never grown: the bound
+// must lie within its allocations.
+static int stream_state_run(fpnn_aes_keyset *ks, uint32_t first, uint32_t count, const uint32_t *slots,
+                            uint32_t slot_bound, const uint8_t *ok, uint8_t *iv_state, uint32_t *pos_state, bool open) {
+    if (!ks || !ks->e) return FPNN_AES_ERR_ARG;
+    if (count == 0) return FPNN_AES_OK;
+    if (!iv_state || !pos_state || ((uintptr_t)iv_state & 15u) || ((uintptr_t)pos_state & 3u) || ((uintptr_t)slots & 3u))
+        return FPNN_AES_ERR_ARG;
+    if (!slots && (uint64_t)first + count > 0xffffffffull) return FPNN_AES_ERR_RANGE;
+    const uint32_t bound = slots ? slot_bound : first + count;
+    if (bound > table_slots(ks)) return FPNN_AES_ERR_ARG;
+    fpnn_aes_engine *e = ks->e;
+    DeviceGuard g(ks->device);
+    KeyTableArgs a;
+    memset(&a, 0, sizeof a);
+    a.keys = ks->d_keys;
+    a.slots = slots;
+    a.first = first;
+    a.count = count;
+    a.slot_bound = bound;
+    a.ok = open ? ok : nullptr;
+    a.iv_state = reinterpret_cast<uint4 *>(iv_state);
+    a.pos_state = pos_state;
+    a.fault = e->d_fault;
+    const BatchScope batch_scope(e);  // (an early return clears the pending flag)
+#ifdef FPNN_AES_BOUNDS
+    if (!e->d_aud) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->d_aud), sizeof(AuditTable)));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    AuditTable t;
+    memset(&t, 0, sizeof t);
+    auto ext = [&](AuditBuf i, const void *p, uint64_t bytes) {
+        if (!p) return;
+        t.lo[i] = (uint64_t)(uintptr_t)p;
+        t.hi[i] = t.lo[i] + bytes;
+    };
+    ext(AB_KEYS, a.keys, sizeof(DevKey) * (uint64_t)table_slots(ks));
+    ext(AB_KT_SLOTS, a.slots, 4 * (uint64_t)a.count);
+    ext(AB_KT_OK, a.ok, a.count);
+    ext(AB_IV_STATE, a.iv_state, 16 * (uint64_t)bound);
+    ext(AB_POS_STATE, a.pos_state, 4 * (uint64_t)bound);
+    HIP_TRY(hipMemcpy(e->d_aud, &t, sizeof t, hipMemcpyHostToDevice));
+    a.aud = e->d_aud;
+#endif
+    HIP_TRY(open ? launch_stream_open(a, e->stream) : launch_stream_close(a, e->stream));
+    batch_queued(e);
+#ifdef FPNN_AES_BOUNDS
+    return audit_end(e, FPNN_AES_OK);
+#else
+    return FPNN_AES_OK;
+#endif
+}
+
+int fpnn_aes_stream_open(fpnn_aes_keyset *ks, uint32_t first, uint32_t count, const uint32_t *slots,
+                         uint32_t slot_bound, const uint8_t *ok, uint8_t *iv_state, uint32_t *pos_state) {
+    return stream_state_run(ks, first, count, slots, slot_bound, ok, iv_state, pos_state, true);
+}
+
+int fpnn_aes_stream_close(fpnn_aes_keyset *ks, uint32_t first, uint32_t count, const uint32_t *slots,
+                          uint32_t slot_bound, uint8_t *iv_state, uint32_t *pos_state) {
+    return stream_state_run(ks, first, count, slots, slot_bound, nullptr, iv_state, pos_state, false);
+}
+
 // ---- batches ---------------------------------------------------------------------
 
 int fpnn_aes_package_encrypt(fpnn_aes_engine *e, const fpnn_aes_batch *b) {
@@ -1572,6 +1676,20 @@ int fpnn_aes_stream_encrypt_frames(fpnn_aes_engine *e, const fpnn_aes_batch *b, 
 int fpnn_aes_stream_decrypt_frames(fpnn_aes_engine *e, const fpnn_aes_batch *b, const uint32_t *first_frame,
                                    uint32_t nstreams, uint8_t *iv_state, uint32_t *pos_state) {
     return run_frames(e, b, first_frame, nstreams, iv_state, pos_state, false);
+}
+
+int fpnn_aes_stream_encrypt_frames_at(fpnn_aes_engine *e, const fpnn_aes_batch *b, const uint32_t *first_frame,
+                                      uint32_t nstreams, const uint32_t *state_slot, uint32_t slot_bound,
+                                      uint8_t *iv_state, uint32_t *pos_state) {
+    const SlotAddr at{state_slot, slot_bound, false};
+    return run_frames(e, b, first_frame, nstreams, iv_state, pos_state, true, &at);
+}
+
+int fpnn_aes_stream_decrypt_frames_at(fpnn_aes_engine *e, const fpnn_aes_batch *b, const uint32_t *first_frame,
+                                      uint32_t nstreams, const uint32_t *state_slot, uint32_t slot_bound,
+                                      uint8_t *iv_state, uint32_t *pos_state) {
+    const SlotAddr at{state_slot, slot_bound, false};
+    return run_frames(e, b, first_frame, nstreams, iv_state, pos_state, false, &at);
 }
 
 // ---- receive side: wire framing on the device ------------------------------------
@@ -1624,16 +1742,20 @@ int fpnn_aes_package_recv(fpnn_aes_engine *e, const fpnn_aes_batch *b, uint32_t 
     return run_decrypt(e, &fb, nullptr, nullptr, false);
 }
 
-int fpnn_aes_stream_recv(fpnn_aes_engine *e, const fpnn_aes_batch *b, uint8_t *iv_state, uint32_t *pos_state,
-                         const uint32_t *carry, uint32_t max_len, uint32_t max_frames, uint64_t *frame_off,
-                         uint32_t *frame_len, fpnn_aes_frame_scan *scan) {
+// at: fpnn_aes_stream_recv_at -- the decrypt is the slot-addressed *_frames path with one
+// frame per stream; the scan is per segment either way.
+static int stream_recv_run(fpnn_aes_engine *e, const fpnn_aes_batch *b, const SlotAddr *at, uint8_t *iv_state,
+                           uint32_t *pos_state, const uint32_t *carry, uint32_t max_len, uint32_t max_frames,
+                           uint64_t *frame_off, uint32_t *frame_len, fpnn_aes_frame_scan *scan) {
     int rc = check_batch(e, b);
     if (rc) return rc;
     if ((rc = debug_fail_point())) return rc;
     if (!b->count) return FPNN_AES_OK;
     if (!frame_off || !frame_len || !scan || !max_frames) return FPNN_AES_ERR_ARG;
     if ((uint64_t)b->count * max_frames > 0xffffffffull) return FPNN_AES_ERR_RANGE;
-    if ((rc = run_decrypt(e, b, iv_state, pos_state, true))) return rc;
+    if (at) rc = run_frames(e, b, nullptr, b->count, iv_state, pos_state, false, at);
+    else rc = run_decrypt(e, b, iv_state, pos_state, true);
+    if (rc) return rc;
     DeviceGuard g(e->device);
     KScan s;
     memset(&s, 0, sizeof s);
@@ -1653,6 +1775,20 @@ int fpnn_aes_stream_recv(fpnn_aes_engine *e, const fpnn_aes_batch *b, uint8_t *i
     HIP_TRY(launch_scan_frames(s, true, e->num_cus, e->stream));
     batch_queued(e);
     return FPNN_AES_OK;
+}
+
+int fpnn_aes_stream_recv(fpnn_aes_engine *e, const fpnn_aes_batch *b, uint8_t *iv_state, uint32_t *pos_state,
+                         const uint32_t *carry, uint32_t max_len, uint32_t max_frames, uint64_t *frame_off,
+                         uint32_t *frame_len, fpnn_aes_frame_scan *scan) {
+    return stream_recv_run(e, b, nullptr, iv_state, pos_state, carry, max_len, max_frames, frame_off, frame_len, scan);
+}
+
+int fpnn_aes_stream_recv_at(fpnn_aes_engine *e, const fpnn_aes_batch *b, const uint32_t *state_slot,
+                            uint32_t slot_bound, uint8_t *iv_state, uint32_t *pos_state, const uint32_t *carry,
+                            uint32_t max_len, uint32_t max_frames, uint64_t *frame_off, uint32_t *frame_len,
+                            fpnn_aes_frame_scan *scan) {
+    const SlotAddr at{state_slot, slot_bound, true};
+    return stream_recv_run(e, b, &at, iv_state, pos_state, carry, max_len, max_frames, frame_off, frame_len, scan);
 }
 
 // ---- single call from host memory ------------------------------------------------

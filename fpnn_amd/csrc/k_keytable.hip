@@ -9,7 +9,10 @@
 //                 must never be seen apart by a later batch.
 //   k_clear_slots the slot becomes what a never-set slot of fpnn_aes_keyset_reserve holds: a
 //                 zero DevKey and the E(0) the rounds give under all-zero round keys.
-// Addressing, both kernels: slot s_i = slots ? slots[i] : first + i.  An entry with
+//   k_stream_open / k_stream_close (fpnn_aes_stream_open / _close): the stream state of a
+//                 slot, (IV, 0) from the slot's DevKey and all zero, in the caller's arrays
+//                 indexed by slot.
+// Addressing, all kernels: slot s_i = slots ? slots[i] : first + i.  An entry with
 // s_i >= slot_bound writes nothing and ORs kFaultKeySlot into the engine's fault word (the
 // next sync returns FPNN_AES_ERR_DEVICE) -- the host sized the table for slot_bound, so no
 // store can leave it whatever slots[] holds.  k_set_keys skips entries with ok[i] == 0.
@@ -144,7 +147,44 @@ __global__ __launch_bounds__(kKtThreads) void k_clear_slots(const KeyTableArgs a
     store_slot(a, s, w, zero, zero, encrypt_block_t0<NR>(zero, w, t0));
 }
 
+// Stream state by slot: a connection's StreamEncryptor starts from (_iv = the connection
+// IV, _pos = 0) (core/Encryptor.h:44-61), and after fpnn_ecdh_accept that IV exists only in
+// the slot's DevKey.  The table is read, the caller's state arrays (slot_bound entries) are
+// written; a cleared or never-set slot holds a zero IV and gives an all-zero state.
+__global__ __launch_bounds__(kKtThreads) void k_stream_open(const KeyTableArgs a) {
+    const uint32_t i = blockIdx.x * kKtThreads + threadIdx.x;
+    if (i >= a.count) return;
+    if (a.ok && *FA_AT(a, AB_KT_OK, a.ok + i, 1) == 0) return;
+    uint32_t s;
+    if (!slot_of(a, i, s)) return;
+    *FA_AT(a, AB_IV_STATE, a.iv_state + s, 16) = *reinterpret_cast<const uint4 *>(FA_AT(a, AB_KEYS, a.keys[s].iv, 16));
+    *FA_AT(a, AB_POS_STATE, a.pos_state + s, 4) = 0u;
+}
+
+__global__ __launch_bounds__(kKtThreads) void k_stream_close(const KeyTableArgs a) {
+    const uint32_t i = blockIdx.x * kKtThreads + threadIdx.x;
+    if (i >= a.count) return;
+    uint32_t s;
+    if (!slot_of(a, i, s)) return;
+    *FA_AT(a, AB_IV_STATE, a.iv_state + s, 16) = make_uint4(0, 0, 0, 0);
+    *FA_AT(a, AB_POS_STATE, a.pos_state + s, 4) = 0u;
+}
+
 }  // namespace
+
+hipError_t launch_stream_open(const KeyTableArgs &a, hipStream_t st) {
+    if (a.count == 0) return hipSuccess;
+    set_launched("stream_open");
+    hipLaunchKernelGGL(k_stream_open, dim3((a.count + kKtThreads - 1) / kKtThreads), dim3(kKtThreads), 0, st, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_stream_close(const KeyTableArgs &a, hipStream_t st) {
+    if (a.count == 0) return hipSuccess;
+    set_launched("stream_close");
+    hipLaunchKernelGGL(k_stream_close, dim3((a.count + kKtThreads - 1) / kKtThreads), dim3(kKtThreads), 0, st, a);
+    return hipGetLastError();
+}
 
 hipError_t launch_set_keys(const KeyTableArgs &a, uint32_t keylen, hipStream_t st) {
     if (a.count == 0) return hipSuccess;

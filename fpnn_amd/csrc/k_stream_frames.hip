@@ -8,6 +8,9 @@
 //         registers from the stream's first frame to its last
 //   decrypt: the state pre-pass (two launches) that gives K1r (k_ragged.hip) every frame's
 //         incoming state from ciphertext alone, and the per-stream commit that follows K1r
+// Every kernel reaches a stream's state through stream_slot(): entry j of the state arrays
+// for the calls above, entry state_slot[j] -- the connection's key-table slot, which is then
+// its key slot too -- for the slot-addressed calls (fpnn_aes_stream_*_frames_at, _recv_at).
 #include "coop.hpp"
 
 namespace fpnn_aes {
@@ -20,12 +23,30 @@ namespace {
 __device__ __forceinline__ void stream_range(const KBatch &b, const FrameTable &f, uint32_t j, uint32_t &f0,
                                              uint32_t &f1) {
     const uint32_t cnt = (uint32_t)b.count;
+    if (!f.first_frame) {  // one frame per stream: stream j is segment j
+        f0 = min(j, cnt);
+        f1 = min(j + 1u, cnt);
+        return;
+    }
     const uint32_t r0 = *FA_AT(b, AB_FIRST_FRAME, f.first_frame + j, 4);
     const uint32_t r1 = *FA_AT(b, AB_FIRST_FRAME, f.first_frame + j + 1, 4);
     const bool bad = r1 < r0 || r1 > cnt || (j == 0 && r0 != 0u) || (j + 1 == f.nstreams && r1 != cnt);
     f0 = min(r0, cnt);
     f1 = max(min(r1, cnt), f0);
     if (bad && f.fault) __hip_atomic_store(f.fault, kFaultFrameTable, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// Where stream j's state lives, and in a slot-addressed call its key: entry s of the state
+// arrays (slot s of b.keys).  Without state_slot that is j.  false: state_slot[j] lies at or
+// past slot_bound -- reported, s = 0, and the caller touches no state for this stream.
+__device__ __forceinline__ bool stream_slot(const KBatch &b, const FrameTable &f, uint32_t j, uint32_t &s) {
+    s = j;
+    if (!f.state_slot) return true;
+    s = *FA_AT(b, AB_STATE_SLOT, f.state_slot + j, 4);
+    if (s < f.slot_bound) return true;
+    if (f.fault) __hip_atomic_fetch_or(f.fault, kFaultKeySlot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    s = 0u;
+    return false;
 }
 
 // One frame's descriptor (no key slot: a stream's frames share one, read once per stream).
@@ -82,18 +103,22 @@ __global__ __launch_bounds__(kThreads, 4) __attribute__((amdgpu_waves_per_eu(4, 
 
     const uint64_t nquads = ((uint64_t)gridDim.x * blockDim.x) >> 2;
     for (uint64_t t = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 2; t < f.nstreams; t += nquads) {
-        uint32_t f0, f1;
+        uint32_t f0, f1, ss;
+        if (!stream_slot(b, f, (uint32_t)t, ss)) continue;  // a slot past the bound: nothing is written
         stream_range(b, f, (uint32_t)t, f0, f1);
         if (f0 >= f1) continue;  // no segment: the state stays as it is
-        const uint32_t slot = (KM == KEY_UNIFORM || !b.key_slot) ? 0u : *FA_AT(b, AB_SLOT, b.key_slot + f0, 4);
+        const uint32_t slot = KM == KEY_UNIFORM ? 0u
+                              : f.state_slot    ? ss
+                              : b.key_slot      ? *FA_AT(b, AB_SLOT, b.key_slot + f0, 4)
+                                                : 0u;
         const DevKey *key = FA_AT(b, AB_KEYS, b.keys + slot, sizeof(DevKey));
         uint32_t rkq[NR + 1];
 #pragma unroll
         for (int r = 0; r <= NR; r++) rkq[r] = key->rk[4 * r + q];
         const uint32_t rkx = rkq[NR] ^ rkq[0];
         // this lane's word of the 16-byte feedback register, and the CFB position
-        uint32_t iv = reinterpret_cast<const uint32_t *>(FA_AT(b, AB_IV_STATE, b.iv_state + 16 * t, 16))[q];
-        uint32_t n = *FA_AT(b, AB_POS_STATE, b.pos_state + t, 4) & 15u;
+        uint32_t iv = reinterpret_cast<const uint32_t *>(FA_AT(b, AB_IV_STATE, b.iv_state + 16ull * ss, 16))[q];
+        uint32_t n = *FA_AT(b, AB_POS_STATE, b.pos_state + ss, 4) & 15u;
 
         FrameDesc cur = frame_desc(b, f0);
         FrameDesc nxt = frame_desc(b, min(f0 + 1u, f1 - 1u));
@@ -231,8 +256,8 @@ __global__ __launch_bounds__(kThreads, 4) __attribute__((amdgpu_waves_per_eu(4, 
                 }
             }
         }
-        reinterpret_cast<uint32_t *>(FA_AT(b, AB_IV_STATE, b.iv_state + 16 * t, 16))[q] = iv;
-        if (q == 0) *FA_AT(b, AB_POS_STATE, b.pos_state + t, 4) = n;
+        reinterpret_cast<uint32_t *>(FA_AT(b, AB_IV_STATE, b.iv_state + 16ull * ss, 16))[q] = iv;
+        if (q == 0) *FA_AT(b, AB_POS_STATE, b.pos_state + ss, 4) = n;
     }
 }
 
@@ -241,21 +266,24 @@ __global__ __launch_bounds__(kThreads, 4) __attribute__((amdgpu_waves_per_eu(4, 
 //   snap_pos[k]   the CFB position frame k starts at, (p0 + bytes of the frames before it) & 15
 //   seg_stream[k] the stream frame k belongs to
 //   seg_prev[k]   the last non-empty frame of the stream before k (~0: none)
+//   seg_slot[k]   slot-addressed calls: the stream's key slot, for K1r's per-segment b.key_slot
 __global__ __launch_bounds__(256) void k_stream_frames_walk(KBatch b, FrameTable f, uint32_t *__restrict__ snap_pos,
                                                             uint32_t *__restrict__ seg_stream,
                                                             uint32_t *__restrict__ seg_prev) {
     const uint64_t nthreads = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < f.nstreams; j += nthreads) {
-        uint32_t f0, f1;
+        uint32_t f0, f1, ss;
+        const bool live = stream_slot(b, f, (uint32_t)j, ss);
         stream_range(b, f, (uint32_t)j, f0, f1);
         if (f0 >= f1) continue;
-        uint32_t n = *FA_AT(b, AB_POS_STATE, b.pos_state + j, 4) & 15u;
+        uint32_t n = live ? *FA_AT(b, AB_POS_STATE, b.pos_state + ss, 4) & 15u : 0u;
         uint32_t prev = ~0u;
         for (uint32_t k = f0; k < f1; k++) {
             const uint32_t len = b.len ? *FA_AT(b, AB_LEN, b.len + k, 4) : b.uniform_len;
             snap_pos[k] = n;
             seg_stream[k] = (uint32_t)j;
             seg_prev[k] = prev;
+            if (f.seg_slot) *FA_AT(b, AB_SEG_SLOT, f.seg_slot + k, 4) = ss;
             if (len) prev = k;
             n = (n + len) & 15u;
         }
@@ -294,12 +322,16 @@ __global__ __launch_bounds__(kThreads) void k_stream_frames_state(KBatch b, Fram
         if (!(k >= f0 && k < f1)) {  // not written by this call's walk
             snap_iv[k] = make_uint4(0, 0, 0, 0);
             snap_pos[k] = 0u;
+            if (f.seg_slot) *FA_AT(b, AB_SEG_SLOT, f.seg_slot + k, 4) = 0u;  // (K1r reads every segment's)
             if (f.fault) __hip_atomic_store(f.fault, kFaultFrameTable, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
             continue;
         }
         const uint32_t pk = snap_pos[k] & 15u;
-        const uint32_t p0 = *FA_AT(b, AB_POS_STATE, b.pos_state + j, 4) & 15u;
-        const uint4 iv0 = *reinterpret_cast<const uint4 *>(FA_AT(b, AB_IV_STATE, b.iv_state + 16ull * j, 16));
+        uint32_t ss;  // (a slot past the bound: a zero state; the walk has reported it)
+        const bool live = stream_slot(b, f, j, ss);
+        const uint32_t p0 = live ? *FA_AT(b, AB_POS_STATE, b.pos_state + ss, 4) & 15u : 0u;
+        const uint4 iv0 = live ? *reinterpret_cast<const uint4 *>(FA_AT(b, AB_IV_STATE, b.iv_state + 16ull * ss, 16))
+                               : make_uint4(0, 0, 0, 0);
         // w: the gathered bytes as one little-endian number, the earliest byte lowest
         uint64_t w0 = 0, w1 = 0, w2 = 0, w3 = 0;
         auto push = [&](uint32_t byte) {
@@ -341,19 +373,21 @@ __global__ __launch_bounds__(kThreads) void k_stream_frames_state(KBatch b, Fram
     }
 }
 
-// After K1r: stream j takes the state its last non-empty frame exported.
+// After K1r: stream j takes the state its last non-empty frame exported (into its slot's
+// entry; a stream whose slot lies past the bound commits nothing).
 __global__ __launch_bounds__(256) void k_stream_frames_commit(KBatch b, FrameTable f, const uint4 *__restrict__ seg_iv,
                                                               const uint32_t *__restrict__ seg_pos) {
     const uint64_t nthreads = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < f.nstreams; j += nthreads) {
-        uint32_t f0, f1;
+        uint32_t f0, f1, ss;
+        if (!stream_slot(b, f, (uint32_t)j, ss)) continue;
         stream_range(b, f, (uint32_t)j, f0, f1);
         for (uint32_t k = f1; k > f0;) {
             k--;
             const uint32_t len = b.len ? *FA_AT(b, AB_LEN, b.len + k, 4) : b.uniform_len;
             if (len) {
-                *reinterpret_cast<uint4 *>(FA_AT(b, AB_IV_STATE, b.iv_state + 16ull * j, 16)) = seg_iv[k];
-                *FA_AT(b, AB_POS_STATE, b.pos_state + j, 4) = seg_pos[k];
+                *reinterpret_cast<uint4 *>(FA_AT(b, AB_IV_STATE, b.iv_state + 16ull * ss, 16)) = seg_iv[k];
+                *FA_AT(b, AB_POS_STATE, b.pos_state + ss, 4) = seg_pos[k];
                 break;
             }
         }

@@ -135,11 +135,24 @@ hipError_t launch_encrypt_coop(const KBatch &b, int nrounds, Layout layout, KeyM
 // b.iv_state / b.pos_state hold nstreams entries.  Every kernel clamps what it reads from
 // first_frame into [0, count] (an empty range when it decreases) and stores
 // kFaultFrameTable into *fault when the table is not monotone from 0 to count.
+//
+// The slot-addressed calls (fpnn_aes_stream_*_frames_at, fpnn_aes_stream_recv_at) set
+// state_slot: stream j's state is entry state_slot[j] of b.iv_state / b.pos_state and its
+// key is slot state_slot[j] of b.keys (b.key_slot is null then); the state arrays hold
+// slot_bound entries.  A stream with state_slot[j] >= slot_bound is reported (kFaultKeySlot
+// ORed into *fault): its state is neither read nor written, encrypt writes nothing for it,
+// decrypt ciphers its segments under slot 0 from a zero state (bytes unspecified, inside
+// its own segments).  state_slot == null is the identity: the calls above.
+// first_frame == null (recv_at): stream j is segment j, nstreams == count.
 struct FrameTable {
-    const uint32_t *first_frame;  // nstreams + 1 entries
+    const uint32_t *first_frame;  // nstreams + 1 entries, or null
     uint32_t nstreams;
-    uint32_t pad;
+    uint32_t slot_bound;          // (with state_slot)
     uint32_t *fault;
+    const uint32_t *state_slot;   // nstreams entries, or null
+    uint32_t *seg_slot;           // decrypt with state_slot: the walk writes every segment's key slot
+                                  // here (count entries, engine scratch); K1r and the pre-pass's
+                                  // second launch read it as b.key_slot
 };
 // K2f: encrypt, one quad per STREAM (K2c's cipher); the quad keeps (iv, pos) in registers
 // across the stream's frames; grid and threads sized as K2c's, by quads needed.
@@ -308,13 +321,20 @@ struct KeyTableArgs {
     uint32_t first, count, slot_bound, pad;
     const uint8_t *raw;   // set_keys: count raw keys of the table's key length
     const uint8_t *ivs;   // set_keys: count * 16 bytes, or null (zero IVs)
-    const uint8_t *ok;    // set_keys: entries with ok[i] == 0 write nothing; or null
+    const uint8_t *ok;    // set_keys, stream_open: entries with ok[i] == 0 write nothing; or null
+    uint4 *iv_state;      // stream_open / _close: the caller's state arrays, slot_bound entries
+    uint32_t *pos_state;
     const uint32_t *t0le;
     uint32_t *fault;
     AuditTable *aud;      // the address-audit build's extent table (null in the product build)
 };
 // one lane per entry: the expanded DevKey and eiv[s_i] = E_k(IV) of the slot, in one launch
 hipError_t launch_set_keys(const KeyTableArgs &a, uint32_t keylen, hipStream_t st);
+// Stream state by slot (fpnn_aes_stream_open / _close), one lane per entry with the same
+// addressing and slot_bound check; the table is only read.  open: iv_state[16 * s_i] = the
+// slot's IV, pos_state[s_i] = 0, skipping entries with ok[i] == 0; close: both become zero.
+hipError_t launch_stream_open(const KeyTableArgs &a, hipStream_t st);
+hipError_t launch_stream_close(const KeyTableArgs &a, hipStream_t st);
 // the slot as fpnn_aes_keyset_reserve leaves it: a zero DevKey and launch_slot_eiv's value for one
 hipError_t launch_clear_slots(const KeyTableArgs &a, int nrounds, hipStream_t st);
 // Host-mapped frame moves: a job copies n segments, segment i from address sbase + soff[i]

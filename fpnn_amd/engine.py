@@ -267,6 +267,17 @@ class Engine:
                                        max_frames, _ptr(off), _ptr(ln), _ptr(scan)), "stream_recv")
         return off, ln, scan
 
+    def stream_recv_at(self, inp, out, count, keys: "KeySet", iv_state, pos_state, state_slot, slot_bound: int,
+                       max_len: int, max_frames: int, carry: Optional[torch.Tensor] = None, **kw):
+        """fpnn_aes_stream_recv_at: stream_recv with segment i's state and key at slot
+        state_slot[i] (no key_slot); returns device tensors (frame_off, frame_len, scan)."""
+        d = self._desc(inp, out, count, keys, **kw)
+        off, ln, scan = self._scan_buffers(count, max_frames, inp.device)
+        check(lib.fpnn_aes_stream_recv_at(self._h, C.byref(d), self._state_slot(state_slot, count), slot_bound,
+                                          _ptr(iv_state), _ptr(pos_state), _ptr(carry), max_len, max_frames, _ptr(off),
+                                          _ptr(ln), _ptr(scan)), "stream_recv_at")
+        return off, ln, scan
+
     # -- ECDH key derivation (include/fpnn_ecdh.h) -------------------------------------------
     @staticmethod
     def ecdh_curve(name: str) -> int:
@@ -407,6 +418,41 @@ class Engine:
         self._frames(lib.fpnn_aes_stream_decrypt_frames, "stream_decrypt_frames", inp, out, count, keys, iv_state,
                      pos_state, first_frame, nstreams, kw)
 
+    # The same by key-table slot: stream j's state is entry state_slot[j] of the state arrays
+    # (slot_bound entries) and its key slot state_slot[j] of `keys`; no key_slot
+    # (fpnn_aes_stream_encrypt_frames_at / _decrypt_frames_at).
+    @staticmethod
+    def _state_slot(state_slot, n):
+        if state_slot is not None:
+            if state_slot.dtype not in (torch.int32, torch.uint32):
+                raise TypeError(f"state_slot: dtype {state_slot.dtype}, expected {torch.int32}")
+            if state_slot.numel() < n:
+                raise ValueError(f"state_slot: {state_slot.numel()} entries for {n} streams")
+        return _ptr(state_slot)
+
+    def _frames_at(self, fn, what, inp, out, count, keys, iv_state, pos_state, first_frame, nstreams, state_slot,
+                   slot_bound, kw):
+        d = self._desc(inp, out, count, keys, **kw)
+        if first_frame is not None:
+            if first_frame.dtype not in (torch.int32, torch.uint32):
+                raise TypeError(f"first_frame: dtype {first_frame.dtype}, expected {torch.int32}")
+            if first_frame.numel() < nstreams + 1:
+                raise ValueError(f"first_frame: {first_frame.numel()} entries for {nstreams} streams")
+        check(fn(self._h, C.byref(d), _ptr(first_frame), nstreams, self._state_slot(state_slot, nstreams), slot_bound,
+                 _ptr(iv_state), _ptr(pos_state)), what)
+
+    def stream_encrypt_frames_at(self, inp, out, count, keys: "KeySet", iv_state: torch.Tensor,
+                                 pos_state: torch.Tensor, first_frame: torch.Tensor, nstreams: int,
+                                 state_slot: torch.Tensor, slot_bound: int, **kw):
+        self._frames_at(lib.fpnn_aes_stream_encrypt_frames_at, "stream_encrypt_frames_at", inp, out, count, keys,
+                        iv_state, pos_state, first_frame, nstreams, state_slot, slot_bound, kw)
+
+    def stream_decrypt_frames_at(self, inp, out, count, keys: "KeySet", iv_state: torch.Tensor,
+                                 pos_state: torch.Tensor, first_frame: torch.Tensor, nstreams: int,
+                                 state_slot: torch.Tensor, slot_bound: int, **kw):
+        self._frames_at(lib.fpnn_aes_stream_decrypt_frames_at, "stream_decrypt_frames_at", inp, out, count, keys,
+                        iv_state, pos_state, first_frame, nstreams, state_slot, slot_bound, kw)
+
 
 def host_register(buf: np.ndarray):
     """fpnn_aes_host_register over a numpy buffer's memory (e.g. a socket-buffer arena):
@@ -527,6 +573,27 @@ class KeySet:
         check(lib.fpnn_aes_keyset_clear(self._h, first, n, sp, sb), "keyset_clear")
         if n:
             self.count = max(self.count, bound)
+
+    # -- stream state by slot (the caller's device arrays, indexed by slot) ---------------------
+    def stream_open(self, iv_state: torch.Tensor, pos_state: torch.Tensor, first: int = 0,
+                    count: Optional[int] = None, *, slots: Optional[torch.Tensor] = None,
+                    slot_bound: Optional[int] = None, ok: Optional[torch.Tensor] = None):
+        """fpnn_aes_stream_open: iv_state[16 * s] = the IV slot s holds, pos_state[s] = 0 for
+        s = slots[i] / first + i, skipping entries with ok[i] == 0; the table is not grown."""
+        n = (slots.numel() if slots is not None else 0) if count is None else count
+        if ok is not None and ok.numel() < n:
+            raise ValueError(f"ok: {ok.numel()} entries for {n} slots")
+        sp, sb, _ = self._addressing(n, first, slots, slot_bound)
+        check(lib.fpnn_aes_stream_open(self._h, first, n, sp, sb, _ptr(ok), _ptr(iv_state), _ptr(pos_state)),
+              "stream_open")
+
+    def stream_close(self, iv_state: torch.Tensor, pos_state: torch.Tensor, first: int = 0,
+                     count: Optional[int] = None, *, slots: Optional[torch.Tensor] = None,
+                     slot_bound: Optional[int] = None):
+        """fpnn_aes_stream_close: the state of the named slots becomes all zero."""
+        n = (slots.numel() if slots is not None else 0) if count is None else count
+        sp, sb, _ = self._addressing(n, first, slots, slot_bound)
+        check(lib.fpnn_aes_stream_close(self._h, first, n, sp, sb, _ptr(iv_state), _ptr(pos_state)), "stream_close")
 
     @classmethod
     def adopt(cls, engine: Engine, h, count: int, keylen: int) -> "KeySet":

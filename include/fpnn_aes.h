@@ -244,6 +244,57 @@ int fpnn_aes_stream_encrypt_frames(fpnn_aes_engine *e, const fpnn_aes_batch *b, 
 int fpnn_aes_stream_decrypt_frames(fpnn_aes_engine *e, const fpnn_aes_batch *b, const uint32_t *first_frame,
                                    uint32_t nstreams, uint8_t *iv_state, uint32_t *pos_state);
 
+/* ---- stream mode by key-table slot: open, cipher, close ------------------------------ */
+/* A connection that lives in slot s of a live key table keeps its stream state at entry s
+ * of the caller's state arrays, so one index names the key and the state, as key_slot does
+ * in fpnn_aes_stream_host.  The arrays are the caller's (DEVICE; iv_state 16-byte aligned,
+ * 16 bytes per slot; pos_state 4 bytes per slot) and hold at least the call's bound; a
+ * connection has two pairs, send and receive.  The life of a connection on the device:
+ *
+ *   fpnn_ecdh_accept / fpnn_aes_keyset_set_keys     key and IV into slot s
+ *   fpnn_aes_stream_open  x 2 (send pair, recv pair) state of s = (IV of s, 0)
+ *   fpnn_aes_stream_*_frames_at / _recv_at           per IO cycle, the active slots only
+ *   fpnn_aes_keyset_clear + fpnn_aes_stream_close x 2   key and state of s are zero
+ *
+ * fpnn_aes_stream_open: iv_state[16*s_i .. +16] = the IV slot s_i holds, pos_state[s_i] = 0
+ * -- what a StreamEncryptor starts from (core/Encryptor.h:44-61) -- for
+ *     s_i = slots ? slots[i] : first + i              (slots: DEVICE, 4-byte aligned, or NULL)
+ * skipping entries with ok != NULL and ok[i] == 0 (the ok[] of fpnn_ecdh_accept: a refused
+ * peer's state is not touched).  A never-set or cleared slot gives an all-zero state.
+ * fpnn_aes_stream_close: the state of every s_i becomes all zero (the last ciphertext block
+ * and the position of a closed connection stop existing).
+ * Both are queued on the stream of the engine that made the key set, read the table, allocate
+ * nothing and wait for nothing; entries of the state arrays that are not named keep every bit.
+ * The bound is first + count, or slot_bound with slots; neither call grows the table: a bound
+ * above fpnn_aes_keyset_capacity is FPNN_AES_ERR_ARG.  An entry with slots[i] >= slot_bound
+ * writes nothing, the other entries are written, and the next fpnn_aes_engine_sync returns
+ * FPNN_AES_ERR_DEVICE once (as fpnn_aes_keyset_set_keys).  FPNN_AES_ERR_ARG also: ks NULL; with
+ * count != 0, NULL or misaligned iv_state / pos_state / slots.  count == 0: FPNN_AES_OK, no-op. */
+int fpnn_aes_stream_open(fpnn_aes_keyset *ks, uint32_t first, uint32_t count,
+        const uint32_t *slots, uint32_t slot_bound, const uint8_t *ok,   /* dev or NULL */
+        uint8_t *iv_state, uint32_t *pos_state);                         /* dev */
+int fpnn_aes_stream_close(fpnn_aes_keyset *ks, uint32_t first, uint32_t count,
+        const uint32_t *slots, uint32_t slot_bound,
+        uint8_t *iv_state, uint32_t *pos_state);
+
+/* fpnn_aes_stream_encrypt_frames / _decrypt_frames with stream j's state at entry
+ * state_slot[j] of the state arrays (which hold slot_bound entries) and the key of all its
+ * frames in slot state_slot[j] of b->keys (state_slot: DEVICE, nstreams entries, 4-byte
+ * aligned).  b->key_slot must be NULL and state_slot must not be (with nstreams != 0), and
+ * slot_bound must not exceed fpnn_aes_keyset_capacity(b->keys): FPNN_AES_ERR_ARG otherwise.
+ * Everything else is as for the *_frames pair.  Entries of the state arrays the call does
+ * not name keep every bit; naming one slot twice in one call is the caller's error.  A
+ * stream with state_slot[j] >= slot_bound has its state neither read nor written; encrypt
+ * writes nothing for it, decrypt leaves the output bytes of its own segments unspecified
+ * and touches no other byte; the other streams are exact, and the next
+ * fpnn_aes_engine_sync returns FPNN_AES_ERR_DEVICE once. */
+int fpnn_aes_stream_encrypt_frames_at(fpnn_aes_engine *e, const fpnn_aes_batch *b, const uint32_t *first_frame,
+                                      uint32_t nstreams, const uint32_t *state_slot, uint32_t slot_bound,
+                                      uint8_t *iv_state, uint32_t *pos_state);
+int fpnn_aes_stream_decrypt_frames_at(fpnn_aes_engine *e, const fpnn_aes_batch *b, const uint32_t *first_frame,
+                                      uint32_t nstreams, const uint32_t *state_slot, uint32_t slot_bound,
+                                      uint8_t *iv_state, uint32_t *pos_state);
+
 /* ---- single call from host memory (the per-frame drop-in) --------------------------- */
 /* Exactly rijndael_cfb_encrypt(ctx, encrypt, in, out, len, ivec, p_num)
  * (base/rijndael.c:1171-1201) with host buffers: stages through pinned memory,
@@ -361,6 +412,13 @@ int fpnn_aes_package_recv(fpnn_aes_engine *e, const fpnn_aes_batch *b, uint32_t 
 int fpnn_aes_stream_recv(fpnn_aes_engine *e, const fpnn_aes_batch *b, uint8_t *iv_state, uint32_t *pos_state,
                          const uint32_t *carry, uint32_t max_len, uint32_t max_frames, uint64_t *frame_off,
                          uint32_t *frame_len, fpnn_aes_frame_scan *scan);
+/* The same with segment i's state AND key at slot state_slot[i] (b->key_slot NULL; the
+ * state arrays hold slot_bound entries; the contracts of fpnn_aes_stream_decrypt_frames_at
+ * with one frame per stream).  carry, the frame tables and scan stay per segment. */
+int fpnn_aes_stream_recv_at(fpnn_aes_engine *e, const fpnn_aes_batch *b, const uint32_t *state_slot,
+                            uint32_t slot_bound, uint8_t *iv_state, uint32_t *pos_state, const uint32_t *carry,
+                            uint32_t max_len, uint32_t max_frames, uint64_t *frame_off, uint32_t *frame_len,
+                            fpnn_aes_frame_scan *scan);
 
 /* ---- memory on an engine's device, for callers built without HIP headers ------------ */
 /* (StreamReceiverBatch uses these: libfpnn_aes.so itself has no HIP dependency, see the

@@ -95,7 +95,11 @@ int fpnn_ecdh_keyset(fpnn_aes_engine *e, int curve, const uint8_t *private_key, 
  * after the call cipher under the new keys with no host wait in between, and no key byte
  * reaches host memory.  After fpnn_aes_engine_reserve with max_segments >= count (and a
  * table that holds the bound) the call allocates nothing and may be captured in a graph.
- * Naming one slot twice in one call is the caller's error. */
+ * Naming one slot twice in one call is the caller's error.
+ * Stream mode: the derived IV stays in the slot; fpnn_aes_stream_open (fpnn_aes.h) with the
+ * same slots and ok writes the connection's initial (iv, pos) state from it, one call per
+ * state pair (send, receive), and the *_frames_at / _recv_at calls then address key and
+ * state by that slot until fpnn_aes_keyset_clear + fpnn_aes_stream_close. */
 int fpnn_ecdh_accept(fpnn_aes_engine *e, int curve, const uint8_t *private_key /*host*/,
         const uint8_t *peer_public /*dev*/, uint32_t count, fpnn_aes_keyset *ks,
         uint32_t first, const uint32_t *slots, uint32_t slot_bound, uint8_t *ok /*dev or NULL*/);

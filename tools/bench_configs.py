@@ -425,6 +425,29 @@ def main():
                "framed_onecall_encrypt_kernel_GiBs": gib(S * L, koe),
                "framed_onecall_decrypt_wall_GiBs": gib(S * L, wod),
                "framed_onecall_decrypt_kernel_GiBs": gib(S * L, kod)}
+        # the same call by key-table slot (*_frames_at): state and key of stream j at slot
+        # state_slot[j] -- identity slots on the same table, then a random permutation (slot
+        # p[j] of a permuted table holds stream j's key, entry p[j] of the state its IV)
+        perm = np.random.default_rng(c["payload_seed"]).permutation(S)
+        inv = np.argsort(perm)
+        ks_p = fpnn_amd.KeySet(eng, keys.reshape(S, -1)[inv].tobytes(), c["keylen"], ivs.reshape(S, 16)[inv].tobytes())
+        iv0_p = torch.from_numpy(np.ascontiguousarray(ivs.reshape(S, 16)[inv]).reshape(-1)).cuda()
+        d_perm = torch.from_numpy(perm.astype(np.int32)).cuda()
+        for tag, kset, ivz, sl in (("identity", ks, iv0, slots), ("permuted", ks_p, iv0_p, d_perm)):
+            def onecall_at(fn, src, dst):
+                st_iv.copy_(ivz)
+                st_pos.zero_()
+                fn(src, dst, nseg, kset, st_iv, st_pos, d1_first, S, sl, S, in_off=d1_offs, lens=d1_lens)
+
+            wae, kae, _ = timed(eng, E, lambda: onecall_at(eng.stream_encrypt_frames_at, a, r), args.reps)
+            assert torch.equal(r, b), tag
+            wad, kad, _ = timed(eng, D, lambda: onecall_at(eng.stream_decrypt_frames_at, b, r), args.reps)
+            assert torch.equal(r, a), tag
+            one.update({f"framed_onecall_at_{tag}_encrypt_wall_GiBs": gib(S * L, wae),
+                        f"framed_onecall_at_{tag}_encrypt_kernel_GiBs": gib(S * L, kae),
+                        f"framed_onecall_at_{tag}_decrypt_wall_GiBs": gib(S * L, wad),
+                        f"framed_onecall_at_{tag}_decrypt_kernel_GiBs": gib(S * L, kad)})
+        del ks_p
         if args.no_host:
             out["C3"] = {"whole_stream_encrypt_kernel_GiBs": gib(S * L, ke),
                          "whole_stream_decrypt_kernel_GiBs": gib(S * L, kd),
