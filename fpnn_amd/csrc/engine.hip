@@ -5,350 +5,16 @@
 // per-packet keys, package vs stream, in-place) and queuing it on the engine's
 // HIP stream.  There is no CPU cipher in this library: every byte of payload is
 // transformed by the HIP kernels in k_encrypt.hip / k_decrypt.hip.
-#include <hip/hip_runtime.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
+// (The calls that take many frames from host memory are in host_frames.hip.)
 #include <sys/random.h>
 
-#include <algorithm>
-#include <atomic>
-#include <climits>
-#include <cstdint>
 #include <chrono>
-#include <condition_variable>
-#include <functional>
-#include <memory>
-#include <mutex>
-#include <string>
-#include <thread>
-#include <unordered_map>
-#include <vector>
 
-#include "../../include/fpnn_aes.h"
 #include "../../include/fpnn_ecdh.h"
 #include "ecc.hpp"
-#include "hostcopy.hpp"
-#include "numa_place.hpp"
-#include "aes_common.hpp"
-#include "kernels.hpp"
+#include "engine_internal.hpp"
 
 using namespace fpnn_aes;
-
-namespace {
-
-thread_local std::string g_last_error;
-
-// FPNN_AES_DEBUG_FAIL_CALL=N (tests only): the N-th host-data call of the process (cfb_host,
-// package_host, stream_host, stream_recv -- the calls the C++ classes make) returns
-// FPNN_AES_ERR_DEVICE as a failed device would, so the drop-in's failure contract can be
-// driven through FPNN's own IO code (fail_policy.hpp, tests/test_gpu_dropin.py).
-int debug_fail_point() {
-    static const long long at = [] {
-        const char *v = getenv("FPNN_AES_DEBUG_FAIL_CALL");
-        return v ? atoll(v) : 0ll;
-    }();
-    if (at <= 0) return 0;
-    static std::atomic<long long> calls{0};
-    if (calls.fetch_add(1, std::memory_order_relaxed) + 1 != at) return 0;
-    g_last_error = "injected device error (FPNN_AES_DEBUG_FAIL_CALL)";
-    return FPNN_AES_ERR_DEVICE;
-}
-
-int hip_fail(hipError_t err, const char *what) {
-    char buf[256];
-    snprintf(buf, sizeof buf, "%s: %s (%d)", what, hipGetErrorString(err), (int)err);
-    g_last_error = buf;
-    return FPNN_AES_ERR_HIP;
-}
-
-#define HIP_TRY(expr)                                          \
-    do {                                                       \
-        hipError_t _e = (expr);                                \
-        if (_e != hipSuccess) return hip_fail(_e, #expr);      \
-    } while (0)
-
-struct EventPair {
-    hipEvent_t beg, end;
-};
-
-// memcpy job of the host-frame gather/scatter
-struct CopyJob {
-    uint8_t *dst;
-    const uint8_t *src;
-    uint64_t n;
-};
-
-// Pinned host memory on `node` (the engine's NUMA placement; < 0: the runtime's default).
-// hipHostMallocNumaUser makes the allocation follow the calling thread's memory policy,
-// which NumaPreferScope points at the node for the call.
-hipError_t pinned_host_alloc(int node, void **p, size_t n) {
-    fpnn_aes::NumaPreferScope prefer(node);
-    return hipHostMalloc(p, n, prefer.active() ? hipHostMallocNumaUser : 0u);
-}
-
-// One slot of the host-frame pipeline (fpnn_aes_package_host / fpnn_aes_stream_host):
-// pinned + device staging and its own stream, so the copies of one chunk overlap the
-// kernel of the other.
-struct HostSlot {
-    uint8_t *h = nullptr, *d = nullptr;
-    uint64_t cap = 0;
-    hipStream_t st = nullptr;
-    hipEvent_t done = nullptr;    // chunk's D2H finished
-    hipEvent_t staged = nullptr;  // chunk's H2D finished (the engine stream may cipher it)
-    hipEvent_t kdone = nullptr;   // chunk's kernel finished (the slot stream may copy it back)
-    bool busy = false;
-    std::vector<CopyJob> scatter;  // staged output -> callers' buffers, run after `done`
-    uint64_t scatter_bytes = 0;
-    // package chunks scatter whole frames [first, first + count) straight from the staged
-    // out_off array instead (no per-frame job list)
-    const fpnn_aes_host_frame *frames = nullptr;
-    uint32_t first = 0, count = 0;
-    uint64_t pre = 0, out_at = 0;
-    const uint64_t *out_off = nullptr;  // pinned, inside h
-};
-
-// One slot of the host-mapped frame pipeline (frames in memory registered with
-// fpnn_aes_host_register): device staging for one chunk (input | output | descriptors),
-// the pinned descriptor block the host fills, and the events that hand the chunk from
-// the move stream to the engine stream and back.
-struct MapSlot {
-    uint8_t *d = nullptr;  // device: in | out | desc
-    uint64_t dcap = 0;
-    uint8_t *h = nullptr;  // pinned: desc
-    uint64_t hcap = 0;
-    hipEvent_t gathered = nullptr;  // chunk staged in HBM (the engine stream may cipher it)
-    hipEvent_t ciphered = nullptr;  // cipher done (the move stream may scatter)
-    hipEvent_t done = nullptr;      // the slot's descriptors went H2D (its pinned block is free)
-    bool busy = false;
-};
-
-// Persistent host workers for the host-frame path.  Gathering 1M separate 1 KiB frames
-// into pinned staging (and scattering the results back) is the host-memory-bound part
-// of fpnn_aes_package_host; threads are kept across calls so a chunk does not pay
-// thread start-up.  run(k, fn) calls fn(0..k-1) across the caller and k-1 workers.
-class HostPool {
-public:
-    // workers run on the engine's NUMA placement (numa_place.hpp: the GPU's node's CPUs)
-    HostPool(unsigned workers, const fpnn_aes::NumaPlacement &pl) : pl_(pl) {
-        for (unsigned t = 0; t < workers; t++) th_.emplace_back([this, t] { loop(t + 1); });
-    }
-    ~HostPool() {
-        {
-            std::lock_guard<std::mutex> lk(mu_);
-            stop_ = true;
-        }
-        cv_.notify_all();
-        for (auto &t : th_) t.join();
-    }
-    // parts a host-frame call splits its copies into: this pool's threads + the caller,
-    // shared fairly among the engines whose host-frame calls run at the same moment (every
-    // engine has a pool of min(16, cores) threads: several IO threads flushing at once would
-    // otherwise oversubscribe the box's CPU share many times over)
-    // (per device: the GPU box grants each GPU its own CPU share)
-    unsigned parts() const {
-        const unsigned all = max_parts();
-        const unsigned active = std::max(1u, g_host_active[device_ & 63].load(std::memory_order_relaxed));
-        return std::max(1u, all / active);
-    }
-    unsigned max_parts() const { return (unsigned)th_.size() + 1; }
-    void set_device(int d) { device_ = d; }
-    static std::atomic<unsigned> g_host_active[64];
-
-    template <class F>
-    void run(unsigned want, const F &fn) {
-        want = std::max(1u, std::min(want, max_parts()));
-        if (want == 1) {
-            fn(0u);
-            return;
-        }
-        const std::function<void(unsigned)> f(fn);
-        {
-            std::lock_guard<std::mutex> lk(mu_);
-            fn_ = &f;
-            active_ = want;
-            pending_ = want - 1;
-            gen_++;
-        }
-        cv_.notify_all();
-        f(0);
-        std::unique_lock<std::mutex> lk(mu_);
-        done_cv_.wait(lk, [this] { return pending_ == 0; });
-        fn_ = nullptr;
-    }
-
-    // memcpy jobs split into contiguous, byte-balanced ranges
-    void copy(const std::vector<CopyJob> &jobs, uint64_t total, unsigned want) {
-        want = std::max(1u, std::min<unsigned>(want, (unsigned)std::min<size_t>(jobs.size(), max_parts())));
-        std::vector<size_t> cut(want + 1, jobs.size());
-        cut[0] = 0;
-        uint64_t acc = 0;
-        unsigned p = 1;
-        for (size_t i = 0; i < jobs.size() && p < want; i++) {
-            acc += jobs[i].n;
-            while (p < want && acc >= total * p / want) cut[p++] = i + 1;
-        }
-        run(want, [&](unsigned q) {
-            for (size_t i = cut[q]; i < cut[q + 1]; i++) copy_streaming(jobs[i].dst, jobs[i].src, jobs[i].n);
-            copy_fence();
-        });
-    }
-
-private:
-    void loop(unsigned me) {
-        (void)fpnn_aes::numa_pin_thread(pl_);
-        uint64_t seen = 0;
-        for (;;) {
-            std::unique_lock<std::mutex> lk(mu_);
-            cv_.wait(lk, [&] { return stop_ || gen_ != seen; });
-            if (stop_) return;
-            seen = gen_;
-            if (me >= active_) continue;
-            const std::function<void(unsigned)> *f = fn_;
-            lk.unlock();
-            (*f)(me);
-            lk.lock();
-            if (--pending_ == 0) done_cv_.notify_one();
-        }
-    }
-
-    const fpnn_aes::NumaPlacement pl_;
-    std::vector<std::thread> th_;
-    std::mutex mu_;
-    std::condition_variable cv_, done_cv_;
-    const std::function<void(unsigned)> *fn_ = nullptr;
-    unsigned active_ = 0, pending_ = 0;
-    uint64_t gen_ = 0;
-    bool stop_ = false;
-    int device_ = 0;
-};
-
-std::atomic<unsigned> HostPool::g_host_active[64];
-
-// a host-frame call in progress on a device (HostPool::parts shares the copy threads
-// among the calls of that device)
-struct HostActive {
-    int d;
-    explicit HostActive(int device) : d(device & 63) { HostPool::g_host_active[d].fetch_add(1, std::memory_order_relaxed); }
-    ~HostActive() { HostPool::g_host_active[d].fetch_sub(1, std::memory_order_relaxed); }
-};
-
-
-}  // namespace
-
-struct fpnn_aes_engine {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    int num_cus = 256;
-    Variant variant;
-    uint8_t *d_tables = nullptr;  // t0le[256] (1 KiB), sbox[256], td0le[256] (1 KiB), isbox[256]
-    // general-layout scratch
-    uint64_t *d_bstart = nullptr;
-    uint64_t cap_bstart = 0;
-    uint4 *d_boundary = nullptr;
-    uint64_t cap_boundary = 0;
-    uint4 *d_snap_iv = nullptr;  // stream-decrypt state snapshot
-    uint64_t cap_snap_iv = 0;
-    uint32_t *d_snap_pos = nullptr;
-    uint64_t cap_snap_pos = 0;
-    uint32_t *d_perm = nullptr;  // ragged encrypt: longest-first order
-    uint64_t cap_perm = 0;
-    uint32_t *d_buckets = nullptr;  // the length-order block (kLengthOrderWords; zeroed when grown, then
-    uint64_t cap_buckets = 0;       // zeroed again by its last reader, kernels.hpp)
-    uint64_t *d_fr_off = nullptr;  // package receive: absolute body offset per frame slot
-    uint64_t cap_fr_off = 0;
-    uint32_t *d_fr_slot = nullptr;  // package receive: key slot per frame slot
-    uint64_t cap_fr_slot = 0;
-    RaggedPlan *d_plan = nullptr;  // K1r: one entry per wave of the decrypt grid
-    uint64_t cap_plan = 0;
-    uint4 *d_sink = nullptr;  // K1r: 2 x uint4 per wave, stores of lanes with nothing to store
-    uint64_t cap_sink = 0;
-    uint64_t *d_desc_off = nullptr;  // K1r: materialized in_off / len of stride / uniform batches
-    uint64_t cap_desc_off = 0;
-    uint32_t *d_desc_len = nullptr;
-    uint64_t cap_desc_len = 0;
-    uint64_t *d_total = nullptr;  // ragged block total (bstart[count]), device only
-    // *_frames decrypt (k_stream_frames.hip), per segment: the stream it belongs to, the
-    // stream's last non-empty frame before it, and the state K1r exports for it
-    uint32_t *d_sf_stream = nullptr;
-    uint64_t cap_sf_stream = 0;
-    uint32_t *d_sf_prev = nullptr;
-    uint64_t cap_sf_prev = 0;
-    uint4 *d_sf_iv = nullptr;
-    uint64_t cap_sf_iv = 0;
-    uint32_t *d_sf_pos = nullptr;
-    uint64_t cap_sf_pos = 0;
-    uint32_t *d_sf_slot = nullptr;  // the slot-addressed (_at) decrypt: every segment's key slot
-    uint64_t cap_sf_slot = 0;
-    uint64_t *d_lookback = nullptr;  // one-pass block map: tickets, epoch, tile status (zeroed when grown)
-    uint64_t cap_lookback = 0;
-    // device-side consistency checks (kFault*): a pinned word kernels may set, read when the
-    // stream is idle (fpnn_aes_engine_sync, synchronous calls) and reported as FPNN_AES_ERR_DEVICE
-    uint32_t *h_fault = nullptr;
-    uint32_t *d_fault = nullptr;
-    uint8_t *d_ecdh = nullptr;  // ECDH host forms / keyset / accept: peers | keys | ivs | ok (grown, kept; every
-                                // call zeroes what it used once its last reader is queued: ecdh_wipe)
-    uint64_t cap_ecdh = 0;
-    uint8_t *d_sstate = nullptr;  // stream host frames: (iv, pos) of the call's streams (grown, kept)
-    uint64_t cap_sstate = 0;
-    uint8_t *h_sstate = nullptr;  // its pinned twin
-    uint64_t cap_hsstate = 0;
-    bool pools = false;            // stream-ordered allocation from `pool` for grow()
-    hipMemPool_t mpool = nullptr;  // the engine's own memory pool (keeps freed scratch for reuse)
-    std::vector<void *> deferred;  // grown-out scratch awaiting an idle stream (no pools)
-    // K0 (k_small.hip): pinned staging of the small synchronous calls, its device view,
-    // and the sequence number the kernel stores when a call is done
-    uint8_t *h_small = nullptr;
-    uint8_t *d_small = nullptr;
-    uint32_t small_seq = 0;
-    // K0s: the resident small-call server's mailbox (pinned), its device view, the last
-    // request number and the epoch of the last server launched (0: none yet)
-    SmallMailbox *h_mb = nullptr;
-    SmallMailbox *d_mb = nullptr;
-    uint32_t mb_seq = 0;
-    uint32_t srv_epoch = 0;
-    // the last batch work this engine queued while small-call servers exist on the device
-    // (a server relaunch on another engine waits for it: batch_fence)
-    hipEvent_t batch_ev = nullptr;
-    std::atomic<bool> batch_pending{false};  // batch kernels about to be queued (batch_signal)
-    std::atomic<bool> batch_ev_live{false};  // batch_ev marks the end of queued batch work
-    uint64_t srv_idle_ticks = 0, srv_life_ticks = 0;
-    // host staging for fpnn_aes_cfb_host
-    uint8_t *h_stage = nullptr;
-    uint8_t *d_stage = nullptr;
-    uint64_t cap_stage = 0;
-    // host-frame pipeline
-    HostSlot hs[3];  // chunk i on slot i % 3: gather(i) runs beside scatter(i - 2)
-    MapSlot ms[4];   // host-mapped chunks: gather(t) + scatter(t - 2) || cipher(t - 1), upload(t + 1)
-    hipStream_t map_stream = nullptr;  // host-mapped moves (both PCIe directions in one launch)
-    const char *host_path = "";  // "host_staged" / "host_mapped": the last host-frame call's path
-    std::unique_ptr<HostPool> pool;  // created on first use
-    fpnn_aes::NumaPlacement numa;    // where the pinned arenas and the pool's threads live
-    // the address-audit build (audit.hpp): the extent table kernels check against
-    AuditTable *d_aud = nullptr;
-    // instrumentation
-    bool timing = false;
-    const char *last_kernel[2] = {"", ""};  // base name of the last main kernel per direction
-    std::vector<EventPair> ev[2];
-    size_t ev_used[2] = {0, 0};
-};
-
-struct fpnn_aes_keyset {
-    fpnn_aes_engine *e = nullptr;  // creating engine (may be destroyed before the key set)
-    int device = 0;
-    DevKey *d_keys = nullptr;
-    uint4 *d_eiv = nullptr;  // E_k(IV) per slot (launch_slot_eiv after every write)
-    uint32_t count = 0;
-    int nrounds = 0;
-    uint32_t keylen = 0;
-    // updatable tables (fpnn_aes_keyset_reserve / _set)
-    uint32_t capacity = 0;
-    DevKey *h_up = nullptr;    // pinned upload staging
-    uint32_t cap_up = 0;       // DevKeys
-    hipEvent_t up_done = nullptr;  // last upload out of h_up
-    bool up_pending = false;
-};
 
 namespace {
 
@@ -362,42 +28,6 @@ const uint8_t *isbox_of(const fpnn_aes_engine *e) { return e->d_tables + 2304; }
 // capacity of its own until it grows)
 uint32_t table_slots(const fpnn_aes_keyset *ks) { return std::max(ks->capacity, ks->count); }
 
-struct DeviceGuard {
-    int prev = -1;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) (void)hipSetDevice(dev);
-    }
-    ~DeviceGuard() {
-        int cur;
-        if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-    }
-};
-
-// Scratch growth on the call path never frees synchronously: hipFree waits for the whole
-// device, so one thread's first large call would stall every other engine's queued work.
-// With stream-ordered pools the old buffer is released by hipFreeAsync behind the work
-// already queued on this engine's stream; without them it is kept until the stream is
-// next idle (engine_sync, the end of a synchronous host call, engine_destroy).
-template <class T>
-int grow(fpnn_aes_engine *e, T *&ptr, uint64_t &cap, uint64_t need) {
-    if (need <= cap) return FPNN_AES_OK;
-    uint64_t n = cap ? cap : 1024;
-    while (n < need) n *= 2;
-    T *np = nullptr;
-    if (e->pools)
-        HIP_TRY(hipMallocFromPoolAsync(reinterpret_cast<void **>(&np), n * sizeof(T), e->mpool, e->stream));
-    else
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&np), n * sizeof(T)));
-    if (ptr) {
-        if (e->pools) HIP_TRY(hipFreeAsync(ptr, e->stream));
-        else e->deferred.push_back(ptr);
-    }
-    ptr = np;
-    cap = n;
-    return FPNN_AES_OK;
-}
-
 // a grow()-managed buffer at engine teardown (the stream is idle)
 void release_scratch(fpnn_aes_engine *e, void *p) {
     if (!p) return;
@@ -410,9 +40,11 @@ void free_deferred(fpnn_aes_engine *e) {  // the engine's stream is idle
     e->deferred.clear();
 }
 
+}  // namespace
+
 // The engine's stream is idle: release grown-out scratch, and report (once) a consistency
 // check a kernel failed since the last look (kernels.hpp, kFault*).
-int stream_idle(fpnn_aes_engine *e) {
+int fpnn_aes::stream_idle(fpnn_aes_engine *e) {
     free_deferred(e);
     const uint32_t f = e->h_fault ? __atomic_exchange_n(e->h_fault, 0u, __ATOMIC_ACQ_REL) : 0u;
     if (!f) return FPNN_AES_OK;
@@ -425,6 +57,8 @@ int stream_idle(fpnn_aes_engine *e) {
                                              : "device-side check failed";
     return FPNN_AES_ERR_DEVICE;
 }
+
+namespace {
 
 // (below, with the small-call server)
 void batch_signal(fpnn_aes_engine *e);
@@ -1005,6 +639,11 @@ int run_frames(fpnn_aes_engine *e, const fpnn_aes_batch *b, const uint32_t *firs
 }
 
 }  // namespace
+
+int fpnn_aes::run_batch(fpnn_aes_engine *e, bool encrypt, const fpnn_aes_batch *b, uint8_t *iv_state,
+                        uint32_t *pos_state, bool stream) {
+    return encrypt ? run_encrypt(e, b, iv_state, pos_state, stream) : run_decrypt(e, b, iv_state, pos_state, stream);
+}
 
 // ===========================================================================
 // C-ABI
@@ -2207,1282 +1846,6 @@ int fpnn_aes_cfb_host(fpnn_aes_engine *e, const fpnn_aes_schedule *ctx, int encr
     memcpy(ivec, h_iv, 16);
     *p_num = *h_pos;
     return FPNN_AES_OK;
-}
-
-// ---- many frames from host memory -----------------------------------------------------
-
-namespace {
-
-// Host threads for gathering/scattering frames: FPNN_AES_HOST_THREADS, default
-// min(16, hardware threads) -- the GPU box grants a 16-CPU share per GPU.
-unsigned host_threads() {
-    unsigned hw = std::thread::hardware_concurrency();
-    unsigned n = std::min(16u, hw ? hw : 1u);
-    if (const char *v = getenv("FPNN_AES_HOST_THREADS")) n = (unsigned)std::max(1, atoi(v));
-    return std::min(n, 64u);  // package chunks keep per-part sums in a 64-entry array
-}
-
-HostPool *pool_of(fpnn_aes_engine *e) {
-    if (!e->pool) {
-        e->pool.reset(new HostPool(host_threads() - 1, e->numa));
-        e->pool->set_device(e->device);
-    }
-    return e->pool.get();
-}
-
-// parts for `bytes` of copying: about 1 MiB per thread at least
-unsigned copy_parts(fpnn_aes_engine *e, uint64_t bytes) {
-    // 1 MiB per copy thread (256 KiB / 64 KiB grains measured within run-to-run spread on
-    // the IO-plumbing echo, profiles/r05/io_multi/r05cg_*; the A/B switch was removed in round 6)
-    constexpr int grain = 20;
-    return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(pool_of(e)->parts(), bytes >> grain));
-}
-
-void parallel_copy(fpnn_aes_engine *e, const std::vector<CopyJob> &jobs, uint64_t total) {
-    pool_of(e)->copy(jobs, total, copy_parts(e, total));
-}
-
-int slot_reserve(HostSlot &s, int node, uint64_t need) {
-    if (!s.st) {
-        HIP_TRY(hipStreamCreateWithFlags(&s.st, hipStreamNonBlocking));
-        HIP_TRY(hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&s.staged, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&s.kdone, hipEventDisableTiming));
-    }
-    if (need <= s.cap) return FPNN_AES_OK;
-    uint64_t n = s.cap ? s.cap : (8u << 20);
-    while (n < need) n *= 2;
-    if (s.h) (void)hipHostFree(s.h);
-    if (s.d) (void)hipFree(s.d);
-    s.h = nullptr;
-    s.d = nullptr;
-    s.cap = 0;
-    HIP_TRY(pinned_host_alloc(node, reinterpret_cast<void **>(&s.h), n));
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s.d), n));
-    s.cap = n;
-    return FPNN_AES_OK;
-}
-
-// FPNN_AES_HOST_STATS=1: per-call breakdown of the host-frame pipeline on stderr
-struct HostStats {
-    bool on = getenv("FPNN_AES_HOST_STATS") != nullptr;
-    double gather = 0, scatter = 0, wait = 0;
-    static double now() {
-        return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-    }
-};
-
-// part p of `parts` of a package chunk's scatter (whole frames, straight from the staged
-// out_off array)
-void scatter_frames_part(const HostSlot &s, unsigned p, unsigned parts) {
-    const uint32_t a = (uint32_t)((uint64_t)s.count * p / parts), b = (uint32_t)((uint64_t)s.count * (p + 1) / parts);
-    for (uint32_t t = a; t < b; t++) {
-        const fpnn_aes_host_frame &f = s.frames[s.first + t];
-        copy_streaming(f.dst, s.h + s.out_at + s.out_off[t], f.len + s.pre);
-    }
-    copy_fence();
-}
-
-// wait for a slot's chunk and scatter its outputs to the callers' buffers
-int slot_drain(fpnn_aes_engine *e, HostSlot &s, HostStats &st) {
-    if (!s.busy) return FPNN_AES_OK;
-    s.busy = false;
-    const double t0 = st.on ? HostStats::now() : 0;
-    HIP_TRY(hipEventSynchronize(s.done));
-    const double t1 = st.on ? HostStats::now() : 0;
-    if (s.frames) {
-        const unsigned parts = copy_parts(e, s.scatter_bytes);
-        pool_of(e)->run(parts, [&](unsigned p) { scatter_frames_part(s, p, parts); });
-        s.frames = nullptr;
-    } else {
-        parallel_copy(e, s.scatter, s.scatter_bytes);
-    }
-    if (st.on) {
-        st.wait += t1 - t0;
-        st.scatter += HostStats::now() - t1;
-    }
-    return FPNN_AES_OK;
-}
-
-}  // namespace
-
-// ---- utilities --------------------------------------------------------------------------
-
-namespace {
-
-// A contiguous part of one frame's bytes, in staging order.
-struct Piece {
-    uint32_t frame, off, len;
-};
-
-// stream-state scratch of the host-frame calls: device (grow(): no free on the call path)
-// and its pinned twin (grown only between calls' uses: the engine stream is drained)
-int sstate_reserve(fpnn_aes_engine *e, uint64_t bytes) {
-    if (int rc = grow(e, e->d_sstate, e->cap_sstate, bytes)) return rc;
-    if (bytes > e->cap_hsstate) {
-        uint64_t c = e->cap_hsstate ? e->cap_hsstate : 4096;
-        while (c < bytes) c *= 2;
-        HIP_TRY(hipStreamSynchronize(e->stream));  // a previous call's state copies are done
-        if (e->h_sstate) (void)hipHostFree(e->h_sstate);
-        e->h_sstate = nullptr;
-        e->cap_hsstate = 0;
-        HIP_TRY(pinned_host_alloc(e->numa.node, reinterpret_cast<void **>(&e->h_sstate), c));
-        e->cap_hsstate = c;
-    }
-    return FPNN_AES_OK;
-}
-
-// Stream-mode host frames grouped by stream: order[] lists the frame indices by key slot,
-// each stream's frames in array order (a stable sort), and segs the streams that carry
-// bytes, in slot order ({slot, first, nframes, bytes}: frames order[first .. +nframes)).
-// A serial counting sort whose first pass also sums each slot's bytes, so the segments
-// come from the histogram, not from a walk of frames[order[i]] (one cache miss per frame
-// in arrival order).  A parallel form on the host pool (per-part histograms, prefix over
-// slot ranges, per-part placement) measured 5-8 ms per 1M frames on the GPU box against
-// this form's 3 (S1, gpurun_out r04k / r04l): four pool passes over a 16-CPU share cost
-// more than they split.  Sparse slot ranges take std::stable_sort.
-struct StreamSeg {
-    uint32_t slot, first, nframes;
-    uint64_t bytes;
-};
-
-void group_streams(const fpnn_aes_host_frame *frames, uint32_t n, uint32_t nkeys, std::vector<uint32_t> &order,
-                   std::vector<StreamSeg> &segs) {
-    order.resize(n);
-    segs.clear();
-    if ((uint64_t)nkeys > 4ull * n + 1024) {  // sparse
-        for (uint32_t i = 0; i < n; i++) order[i] = i;
-        std::stable_sort(order.begin(), order.end(),
-                         [frames](uint32_t x, uint32_t y) { return frames[x].key_slot < frames[y].key_slot; });
-        for (uint32_t i = 0; i < n;) {
-            const uint32_t slot = frames[order[i]].key_slot;
-            uint32_t j = i;
-            uint64_t bytes = 0;
-            while (j < n && frames[order[j]].key_slot == slot) bytes += frames[order[j++]].len;
-            if (bytes) segs.push_back({slot, i, j - i, bytes});  // empty streams keep their state
-            i = j;
-        }
-        return;
-    }
-    std::vector<uint32_t> cnt((size_t)nkeys + 1, 0);
-    std::vector<uint64_t> byt(nkeys, 0);
-    for (uint32_t i = 0; i < n; i++) {
-        cnt[frames[i].key_slot + 1]++;
-        byt[frames[i].key_slot] += frames[i].len;
-    }
-    for (uint32_t k = 0; k < nkeys; k++) {
-        if (byt[k]) segs.push_back({k, cnt[k], cnt[k + 1], byt[k]});
-        cnt[k + 1] += cnt[k];
-    }
-    for (uint32_t i = 0; i < n; i++) order[cnt[frames[i].key_slot]++] = i;
-}
-
-// Host-frame pipeline shared by the package and stream entry points.
-//   package: one segment per frame (key slot frames[i].key_slot, fresh chain).
-//   stream : one segment per distinct stream slot = the concatenation of that
-//            stream's frames in array order (CFB over a concatenation equals the
-//            successive calls, base/rijndael.c:1171-1201 carries ivec/num), whose
-//            state lives in iv_state/pos_state[slot] on the host.
-// Chunks of <= kChunk input bytes are gathered into pinned staging by the copy pool,
-// then H2D and D2H run on the slot's stream and the kernel on the engine stream (events
-// hand the chunk over) while the host gathers the next chunk.  Kernels of successive
-// chunks are therefore ordered: they share the engine's scratch, and in stream mode a
-// stream split across chunks continues from the state the previous chunk left.
-int host_pipeline(fpnn_aes_engine *e, bool encrypt, bool stream, const fpnn_aes_host_frame *frames, uint32_t n,
-                  const fpnn_aes_keyset *keys, uint32_t flags, uint8_t *iv_state, uint32_t *pos_state) {
-    const HostActive active_call(e->device);
-    const uint64_t pre = (!stream && (flags & FPNN_AES_F_WIRE_PREFIX)) ? 4 : 0;
-    // input bytes per pipeline chunk.  (Quarter-call chunks for small calls, so one IO
-    // cycle's 8 MiB flush would overlap its steps, measured slower: 1.37 against 0.83 ms
-    // per flush, each chunk's copies getting fewer threads, gpurun_out r05d.)
-    const uint64_t kChunk = 32ull << 20;
-    // ---- segments in staging order -------------------------------------------------
-    std::vector<uint32_t> order;  // frame indices
-    std::vector<StreamSeg> segs;  // stream mode only (package chunks walk `frames` directly)
-    if (stream) group_streams(frames, n, keys->count, order, segs);
-    if (stream && segs.empty()) return FPNN_AES_OK;
-    e->host_path = "host_staged";
-    const uint64_t nseg = stream ? segs.size() : n;
-    HostStats hst;
-    const double t_call = hst.on ? HostStats::now() : 0;
-    uint64_t nchunks = 0;
-    DeviceGuard g(e->device);
-    hipStream_t main_stream = e->stream;
-    // order the slot streams after work already queued on the engine stream
-    for (auto &sl : e->hs)
-        if (int rc = slot_reserve(sl, e->numa.node, 0)) return rc;
-    HIP_TRY(hipEventRecord(e->hs[0].kdone, main_stream));
-    for (auto &sl : e->hs) HIP_TRY(hipStreamWaitEvent(sl.st, e->hs[0].kdone, 0));
-    // ---- stream state: compact (iv, pos) of the touched streams on the device ----------
-    uint8_t *d_state = nullptr, *h_state = nullptr;
-    // stream round-robin cursors: bytes left, frame cursor, host model of pos (for the
-    // decrypt block count) per segment
-    struct {
-        std::vector<uint64_t> rem;
-        std::vector<uint32_t> fi, fo, pos;
-        uint64_t left = 0, next = 0, chunk = 0, quota = 0;
-    } sr;
-    if (stream) {
-        const uint64_t bytes = nseg * 20;
-        if (int rc = sstate_reserve(e, bytes)) return rc;
-        h_state = e->h_sstate;
-        d_state = e->d_sstate;
-        // (a fresh d_state is stream-ordered on the engine stream: the upload below waits for it)
-        HIP_TRY(hipEventRecord(e->hs[0].kdone, main_stream));
-        HIP_TRY(hipStreamWaitEvent(e->hs[0].st, e->hs[0].kdone, 0));
-        sr.rem.resize(nseg);
-        sr.fi.assign(nseg, 0);
-        sr.fo.assign(nseg, 0);
-        sr.pos.resize(nseg);
-        uint32_t *hp = reinterpret_cast<uint32_t *>(h_state + 16 * nseg);
-        for (uint64_t t = 0; t < nseg; t++) {
-            memcpy(h_state + 16 * t, iv_state + 16ull * segs[t].slot, 16);
-            hp[t] = sr.pos[t] = pos_state[segs[t].slot] & 15u;
-            sr.rem[t] = segs[t].bytes;
-            sr.left += segs[t].bytes;
-        }
-        // bigger chunks for few long streams (more chain steps per launch), quota per
-        // stream so one chunk spans as many streams as it can
-        sr.chunk = std::min<uint64_t>(256ull << 20, std::max<uint64_t>(kChunk, sr.left / 4));
-        sr.quota = std::max<uint64_t>(16u << 10, (sr.chunk / nseg + 15) & ~15ull);
-        (void)hipMemcpyAsync(d_state, h_state, bytes, hipMemcpyHostToDevice, e->hs[0].st);
-    }
-    int rc = FPNN_AES_OK;
-    uint64_t si = 0;  // package: next segment; stream: nseg once every byte is queued
-    int k = 0;
-    HostSlot *prev = nullptr;
-    std::vector<Piece> pieces;
-    std::vector<CopyJob> gather;
-    const int kSlots = (int)(sizeof(e->hs) / sizeof(e->hs[0]));
-    while (si < nseg && rc == FPNN_AES_OK) {
-        HostSlot &s = e->hs[k];
-        if ((rc = slot_drain(e, s, hst))) break;  // package: already scattered beside a gather
-        // package: the chunk two back is scattered by half the copy threads while the other
-        // half gathers this one (host memory, not one thread group, is the limit)
-        HostSlot *sc = nullptr;
-        if (!stream) {
-            HostSlot &o = e->hs[(k + 1) % kSlots];
-            if (o.busy && o.frames) {
-                const double tw = hst.on ? HostStats::now() : 0;
-                HIP_TRY(hipEventSynchronize(o.done));
-                if (hst.on) hst.wait += HostStats::now() - tw;
-                o.busy = false;
-                sc = &o;
-            }
-        }
-        // ---- choose this chunk's segments / pieces ----
-        pieces.clear();
-        struct CSeg {
-            uint32_t slot;
-            uint64_t at, len;
-            uint32_t pos;
-        };
-        std::vector<CSeg> cs;
-        uint64_t state0 = si;  // stream: state index of the chunk's first segment
-        uint64_t in_b = 0;
-        uint32_t cnt = 0, uni_len = 0;  // uni_len: stream chunk whose segments all take this many bytes
-        uint64_t out_b = 0, in_pad = 0, out_pad = 0, arr = 0, out_at = 0;
-        if (!stream) {
-            // whole frames [si, j) with <= kChunk input bytes (at least one frame)
-            uint64_t j = si;
-            while (j < n && (j == si || in_b + frames[j].len <= kChunk)) in_b += frames[j++].len;
-            cnt = (uint32_t)(j - si);
-            out_b = in_b + pre * cnt;
-            in_pad = (in_b + 15) & ~15ull;
-            out_pad = (out_b + 15) & ~15ull;
-            arr = (uint64_t)cnt * (8 + 8 + 4 + 4);
-            out_at = in_pad + ((arr + 15) & ~15ull);
-            if ((rc = slot_reserve(s, e->numa.node, in_pad + out_pad + arr + 64))) break;
-            uint64_t *in_off = reinterpret_cast<uint64_t *>(s.h + in_pad);
-            uint64_t *out_off = in_off + cnt;
-            uint32_t *lens = reinterpret_cast<uint32_t *>(out_off + cnt);
-            uint32_t *slots = lens + cnt;
-            // frame-parallel: per-part byte sums, then offsets + arrays + gather per part
-            const unsigned all = pool_of(e)->parts();
-            const unsigned sparts = sc ? std::max(1u, all / 2) : 0;
-            const unsigned parts = sc ? std::max(1u, all - sparts) : copy_parts(e, in_b);
-            uint64_t psum[64 + 1] = {0};
-            const fpnn_aes_host_frame *fr = frames + si;
-            auto range = [&](unsigned p, uint32_t &a, uint32_t &b) {
-                a = (uint32_t)((uint64_t)cnt * p / parts);
-                b = (uint32_t)((uint64_t)cnt * (p + 1) / parts);
-            };
-            const double tg = hst.on ? HostStats::now() : 0;
-            pool_of(e)->run(parts, [&](unsigned p) {
-                uint32_t a, b;
-                range(p, a, b);
-                uint64_t sum = 0;
-                for (uint32_t t = a; t < b; t++) sum += fr[t].len;
-                psum[p + 1] = sum;
-            });
-            for (unsigned p = 0; p < parts; p++) psum[p + 1] += psum[p];
-            uint8_t *h_in = s.h;
-            pool_of(e)->run(parts + sparts, [&](unsigned p) {
-                if (p >= parts) {
-                    scatter_frames_part(*sc, p - parts, sparts);
-                    return;
-                }
-                uint32_t a, b;
-                range(p, a, b);
-                uint64_t io = psum[p], oo = psum[p] + pre * a;
-                for (uint32_t t = a; t < b; t++) {
-                    const fpnn_aes_host_frame &f = fr[t];
-                    in_off[t] = io;
-                    out_off[t] = oo;
-                    lens[t] = f.len;
-                    slots[t] = f.key_slot;
-                    copy_streaming(h_in + io, f.src, f.len);
-                    io += f.len;
-                    oo += f.len + pre;
-                }
-                copy_fence();
-            });
-            if (hst.on) hst.gather += HostStats::now() - tg;
-            if (sc) sc->frames = nullptr;
-            s.frames = frames;
-            s.first = (uint32_t)si;
-            s.count = cnt;
-            s.pre = pre;
-            s.out_at = out_at;
-            s.out_off = out_off;
-            s.scatter_bytes = out_b;
-            si = j;
-        } else {
-            // Round robin: each chunk takes up to `quota` bytes from each of a run of
-            // consecutive streams, so every kernel advances many CFB chains at once (the
-            // encrypt chain is serial: parallelism = streams per kernel).
-            uint64_t t = sr.next < nseg ? sr.next : 0;
-            while (sr.rem[t] == 0) t = t + 1 < nseg ? t + 1 : 0;  // left_total > 0: terminates
-            state0 = t;
-            for (; t < nseg && in_b < sr.chunk; t++) {
-                const StreamSeg &sg = segs[t];
-                const uint64_t take = std::min(sr.rem[t], sr.quota);
-                uint64_t took = 0;
-                while (took < take) {
-                    const fpnn_aes_host_frame &f = frames[order[sg.first + sr.fi[t]]];
-                    const uint32_t part = (uint32_t)std::min<uint64_t>(f.len - sr.fo[t], take - took);
-                    if (part) pieces.push_back({order[sg.first + sr.fi[t]], sr.fo[t], part});
-                    took += part;
-                    sr.fo[t] += part;
-                    if (sr.fo[t] == f.len) {
-                        sr.fi[t]++;
-                        sr.fo[t] = 0;
-                    }
-                }
-                cs.push_back({sg.slot, in_b, take, sr.pos[t]});
-                sr.pos[t] = (uint32_t)((sr.pos[t] + take) & 15u);
-                sr.rem[t] -= take;
-                sr.left -= take;
-                in_b += take;
-            }
-            sr.next = t;
-            if (sr.left == 0) si = nseg;
-            // stream chunk: arrays and gather/scatter jobs from the pieces
-            cnt = (uint32_t)cs.size();
-            out_b = in_b;
-            in_pad = (in_b + 15) & ~15ull;
-            out_pad = in_pad;
-            arr = (uint64_t)cnt * (8 + 8 + 4 + 4);
-            out_at = in_pad + ((arr + 15) & ~15ull);
-            if ((rc = slot_reserve(s, e->numa.node, in_pad + out_pad + arr + 64))) break;
-            uint64_t *in_off = reinterpret_cast<uint64_t *>(s.h + in_pad);
-            uint64_t *out_off = in_off + cnt;
-            uint32_t *lens = reinterpret_cast<uint32_t *>(out_off + cnt);
-            uint32_t *slots = lens + cnt;
-            uni_len = cnt ? (uint32_t)cs[0].len : 0u;
-            for (uint32_t t = 0; t < cnt; t++) {
-                in_off[t] = out_off[t] = cs[t].at;
-                lens[t] = (uint32_t)cs[t].len;
-                slots[t] = cs[t].slot;
-                if (lens[t] != uni_len) uni_len = 0;
-            }
-            gather.clear();
-            s.scatter.clear();
-            s.scatter_bytes = in_b;
-            uint64_t at = 0;
-            for (const Piece &pc : pieces) {
-                const fpnn_aes_host_frame &f = frames[pc.frame];
-                gather.push_back({s.h + at, f.src + pc.off, pc.len});
-                s.scatter.push_back({f.dst + pc.off, s.h + out_at + at, pc.len});
-                at += pc.len;
-            }
-            const double tg = hst.on ? HostStats::now() : 0;
-            parallel_copy(e, gather, in_b);
-            if (hst.on) hst.gather += HostStats::now() - tg;
-        }
-        nchunks++;
-        HIP_TRY(hipMemcpyAsync(s.d, s.h, in_pad + arr, hipMemcpyHostToDevice, s.st));
-        // The cipher runs on the engine stream: chunks share the engine's scratch (block
-        // map, plan, length order, queue counter), so their kernels must not overlap --
-        // and stream chunks continue from the state the previous chunk left.  The copies
-        // of the slots still overlap each other and the kernels.
-        HIP_TRY(hipEventRecord(s.staged, s.st));
-        HIP_TRY(hipStreamWaitEvent(main_stream, s.staged, 0));
-        fpnn_aes_batch b;
-        memset(&b, 0, sizeof b);
-        b.in = s.d;
-        b.out = s.d + out_at;
-        b.count = cnt;
-        b.in_off = reinterpret_cast<const uint64_t *>(s.d + in_pad);
-        b.out_off = pre ? b.in_off + cnt : nullptr;
-        b.len = reinterpret_cast<const uint32_t *>(s.d + in_pad + 16ull * cnt);
-        b.key_slot = keys->count > 1 ? b.len + cnt : nullptr;
-        if (stream && encrypt && uni_len) {
-            // every stream takes the same quota (segments back to back): a uniform batch,
-            // so the encrypt skips the ragged length ordering (mapped_stream_pipeline)
-            b.in_off = nullptr;
-            b.len = nullptr;
-            b.stride = uni_len;
-            b.uniform_len = uni_len;
-        }
-        b.keys = keys;
-        b.flags = pre ? FPNN_AES_F_WIRE_PREFIX : 0;
-        uint8_t *ivp = stream ? d_state + 16 * state0 : nullptr;
-        uint32_t *posp = stream ? reinterpret_cast<uint32_t *>(d_state + 16 * nseg) + state0 : nullptr;
-        rc = encrypt ? run_encrypt(e, &b, ivp, posp, stream) : run_decrypt(e, &b, ivp, posp, stream);
-        if (rc) break;
-        HIP_TRY(hipEventRecord(s.kdone, main_stream));
-        HIP_TRY(hipStreamWaitEvent(s.st, s.kdone, 0));
-        HIP_TRY(hipMemcpyAsync(s.h + out_at, s.d + out_at, out_pad, hipMemcpyDeviceToHost, s.st));
-        HIP_TRY(hipEventRecord(s.done, s.st));
-        s.busy = true;
-        prev = &s;
-        k = (k + 1) % kSlots;
-    }
-    for (auto &sl : e->hs) {
-        const int r2 = slot_drain(e, sl, hst);
-        if (!rc) rc = r2;
-    }
-    if (stream) {
-        if (!rc && prev) {
-            const hipError_t err = hipMemcpy(h_state, d_state, nseg * 20, hipMemcpyDeviceToHost);
-            if (err != hipSuccess) rc = hip_fail(err, "hipMemcpy(stream state)");
-        }
-        if (!rc) {
-            const uint32_t *hp = reinterpret_cast<const uint32_t *>(h_state + 16 * nseg);
-            for (uint64_t t = 0; t < nseg; t++) {
-                memcpy(iv_state + 16ull * segs[t].slot, h_state + 16 * t, 16);
-                pos_state[segs[t].slot] = hp[t];
-            }
-        }
-    }
-    if (hst.on)
-        fprintf(stderr, "[fpnn_aes host] %s %s: %u frames, %llu segments, %llu chunks, %.2f ms total, gather %.2f, "
-                "scatter %.2f, wait %.2f ms, %u copy threads\n", stream ? "stream" : "package",
-                encrypt ? "encrypt" : "decrypt", n, (unsigned long long)nseg, (unsigned long long)nchunks,
-                1e3 * (HostStats::now() - t_call), 1e3 * hst.gather, 1e3 * hst.scatter, 1e3 * hst.wait,
-                e->pool ? e->pool->parts() : 1u);
-    return rc;
-}
-
-int check_host_frames(const fpnn_aes_engine *e, const fpnn_aes_host_frame *frames, uint32_t n,
-                      const fpnn_aes_keyset *keys) {
-    if (!e || !keys || (n && !frames)) return FPNN_AES_ERR_ARG;
-    if (keys->device != e->device) return FPNN_AES_ERR_ARG;
-    for (uint32_t i = 0; i < n; i++)
-        if ((frames[i].len && (!frames[i].src || !frames[i].dst)) || frames[i].key_slot >= keys->count)
-            return FPNN_AES_ERR_ARG;
-    return FPNN_AES_OK;
-}
-
-// ---- host-mapped frames ------------------------------------------------------------------
-// Host ranges registered with fpnn_aes_host_register (process-wide, portable: every GPU may
-// access them).  A range's device-visible address is looked up per device on first use.
-constexpr int kMapDevices = 64;
-struct MappedRange {
-    uintptr_t lo, hi;
-    intptr_t delta[kMapDevices];  // device address - host address per device (INTPTR_MIN: not looked up)
-};
-std::mutex g_map_mu;
-std::vector<MappedRange> g_mapped;  // sorted by lo, disjoint
-
-// One call's view of the registry: the ranges and this device's address deltas.
-struct MapView {
-    std::vector<uintptr_t> lo, hi;
-    std::vector<intptr_t> delta;
-    // the range holding [p, p + n), or -1
-    long find(const void *ptr, uint64_t n) const {
-        const uintptr_t p = (uintptr_t)ptr;
-        auto it = std::upper_bound(lo.begin(), lo.end(), p);
-        if (it == lo.begin()) return -1;
-        const size_t i = (size_t)(it - lo.begin()) - 1;
-        return p + n <= hi[i] && p + n >= p ? (long)i : -1;
-    }
-};
-
-int map_view(int device, MapView &v) {
-    std::lock_guard<std::mutex> lk(g_map_mu);
-    v.lo.clear();
-    v.hi.clear();
-    v.delta.clear();
-    if (device < 0 || device >= kMapDevices) return FPNN_AES_OK;  // (no mapped path there)
-    for (auto &r : g_mapped) {
-        if (r.delta[device] == INTPTR_MIN) {
-            DeviceGuard g(device);
-            void *dp = nullptr;
-            HIP_TRY(hipHostGetDevicePointer(&dp, reinterpret_cast<void *>(r.lo), 0));
-            r.delta[device] = (intptr_t)dp - (intptr_t)r.lo;
-        }
-        v.lo.push_back(r.lo);
-        v.hi.push_back(r.hi);
-        v.delta.push_back(r.delta[device]);
-    }
-    return FPNN_AES_OK;
-}
-
-int mslot_reserve(MapSlot &m, int node, uint64_t dneed, uint64_t hneed) {
-    if (!m.gathered) {
-        HIP_TRY(hipEventCreateWithFlags(&m.gathered, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&m.ciphered, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&m.done, hipEventDisableTiming));
-    }
-    if (dneed > m.dcap) {
-        uint64_t c = m.dcap ? m.dcap : (16u << 20);
-        while (c < dneed) c *= 2;
-        if (m.d) (void)hipFree(m.d);
-        m.d = nullptr;
-        m.dcap = 0;
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&m.d), c));
-        m.dcap = c;
-    }
-    if (hneed > m.hcap) {
-        uint64_t c = m.hcap ? m.hcap : (1u << 20);
-        while (c < hneed) c *= 2;
-        if (m.h) (void)hipHostFree(m.h);
-        m.h = nullptr;
-        m.hcap = 0;
-        HIP_TRY(pinned_host_alloc(node, reinterpret_cast<void **>(&m.h), c));
-        m.hcap = c;
-    }
-    return FPNN_AES_OK;
-}
-
-// Package-mode host frames that all lie in registered memory.  The call is cut into
-// chunks of whole frames; chunk t lives in slot t % 4 (HBM staging in | out | descriptors,
-// pinned descriptor block).  Step t: on the move stream ONE launch gathers chunk t from
-// host memory into its staging AND scatters chunk t - 2's results to the frames'
-// destinations (k_move_segments: both PCIe directions busy in one kernel); meanwhile the
-// engine stream ciphers chunk t - 1 as an ordinary device batch (uniform lengths keep the
-// dense K2 / K1d paths) and then uploads chunk t + 1's descriptors (40 B per frame,
-// written by the host threads during step t), so the move stream never waits for a copy.
-// Events hand each chunk between the two streams.  The host threads only write
-// descriptors.
-int mapped_pipeline(fpnn_aes_engine *e, bool encrypt, const fpnn_aes_host_frame *frames, uint32_t n,
-                    const fpnn_aes_keyset *keys, uint32_t flags, const MapView &v, uint32_t *done) {
-    const HostActive active_call(e->device);
-    const uint64_t pre = (flags & FPNN_AES_F_WIRE_PREFIX) ? 4 : 0;
-    static const uint64_t kChunk = [] {     // input bytes per full chunk (FPNN_AES_MAP_CHUNK_MB)
-        const char *x = getenv("FPNN_AES_MAP_CHUNK_MB");
-        return (x && atoi(x) > 0 ? (uint64_t)atoi(x) : 32ull) << 20;
-    }();
-    const uint32_t kMaxFrames = 1u << 20;   // frames per chunk (descriptor block <= 40 MiB)
-    constexpr int kSlots = (int)(sizeof(e->ms) / sizeof(e->ms[0]));
-    static_assert(kSlots >= 4, "a chunk's staging is live for three steps, plus the upload ahead");
-    HostStats hst;
-    const double t_call = hst.on ? HostStats::now() : 0;
-    DeviceGuard g(e->device);
-    for (auto &m : e->ms)
-        if (int rc = mslot_reserve(m, e->numa.node, 0, 0)) return rc;
-    if (!e->map_stream) HIP_TRY(hipStreamCreateWithFlags(&e->map_stream, hipStreamNonBlocking));
-    hipStream_t ms = e->map_stream;
-    // the move stream starts after work already queued on the engine stream
-    HIP_TRY(hipEventRecord(e->ms[0].ciphered, e->stream));
-    HIP_TRY(hipStreamWaitEvent(ms, e->ms[0].ciphered, 0));
-    struct Chunk {
-        uint32_t first = 0, cnt = 0;  // cnt = 0: no chunk in the slot
-        bool uniform = false;
-        uint64_t out_at = 0, desc_at = 0, desc_b = 0;
-    } ch[kSlots];
-    auto jobs_of = [&](int slot, MoveJob &gather, MoveJob &scatter) {
-        const Chunk &c = ch[slot];
-        MapSlot &m = e->ms[slot];
-        const uint64_t *d_src = reinterpret_cast<const uint64_t *>(m.d + c.desc_at);
-        const uint64_t *d_so = d_src + c.cnt, *d_dst = d_so + c.cnt, *d_oo = d_dst + c.cnt;
-        const uint32_t *d_len = reinterpret_cast<const uint32_t *>(d_oo + c.cnt);
-        gather = MoveJob{0, d_src, (uint64_t)(uintptr_t)m.d, d_so, d_len, 0, c.cnt};
-        scatter = MoveJob{(uint64_t)(uintptr_t)(m.d + c.out_at), d_oo, 0, d_dst, d_len, (uint32_t)pre, c.cnt};
-    };
-    uint32_t si = 0;
-    bool stop = false;  // a frame outside registered memory ended the mapped chunks
-    // host: the descriptors of chunk t into its slot's pinned block (false: no chunk t)
-    auto prepare = [&](uint64_t t, int &rc) -> bool {
-        const int k = (int)(t % kSlots);
-        Chunk &c = ch[k];
-        c.cnt = 0;
-        if (si >= n || stop) return false;
-        MapSlot &m = e->ms[k];
-        if (m.busy) {  // the slot's previous pinned block went H2D
-            const double tw = hst.on ? HostStats::now() : 0;
-            if (hipError_t err = hipEventSynchronize(m.done)) {
-                rc = hip_fail(err, "hipEventSynchronize");
-                return false;
-            }
-            if (hst.on) hst.wait += HostStats::now() - tw;
-            m.busy = false;
-        }
-        const double tf = hst.on ? HostStats::now() : 0;
-        uint64_t in_b = 0;
-        uint32_t j = si;
-        while (j < n && (j == si || (in_b + frames[j].len <= kChunk && j - si < kMaxFrames))) in_b += frames[j++].len;
-        uint32_t cnt = j - si;
-        const fpnn_aes_host_frame *fr = frames + si;
-        // every frame of the chunk inside registered memory?  The chunk ends before the
-        // first one that is not (the caller takes the rest through the staged path).
-        {
-            const unsigned parts = cnt >= 16384 ? pool_of(e)->parts() : 1u;
-            std::atomic<uint32_t> bad{cnt};
-            pool_of(e)->run(parts, [&](unsigned p) {
-                const uint32_t a0 = (uint32_t)((uint64_t)cnt * p / parts), b0 = (uint32_t)((uint64_t)cnt * (p + 1) / parts);
-                long rs = -1, rd = -1;
-                for (uint32_t q = a0; q < b0; q++) {
-                    const fpnn_aes_host_frame &f = fr[q];
-                    const uintptr_t xs = (uintptr_t)f.src, xd = (uintptr_t)f.dst;
-                    bool ok = true;
-                    if (f.len && (rs < 0 || xs < v.lo[rs] || xs + f.len > v.hi[rs])) ok = (rs = v.find(f.src, f.len)) >= 0;
-                    if (ok && f.len + pre && (rd < 0 || xd < v.lo[rd] || xd + f.len + pre > v.hi[rd]))
-                        ok = (rd = v.find(f.dst, f.len + pre)) >= 0;
-                    if (!ok) {
-                        uint32_t cur = bad.load();
-                        while (q < cur && !bad.compare_exchange_weak(cur, q)) {
-                        }
-                        return;
-                    }
-                }
-            });
-            if (bad.load() < cnt) {
-                cnt = bad.load();
-                j = si + cnt;
-                in_b = 0;
-                for (uint32_t q = 0; q < cnt; q++) in_b += fr[q].len;
-                stop = true;  // no chunk after this one
-                if (!cnt) return false;
-            }
-        }
-        const uint64_t out_b = in_b + pre * cnt;
-        const uint64_t in_pad = (in_b + 255) & ~255ull, out_pad = (out_b + 255) & ~255ull;
-        c.first = si;
-        c.out_at = in_pad;
-        c.desc_at = in_pad + out_pad;
-        c.desc_b = (uint64_t)cnt * 40;
-        if (c.desc_at + c.desc_b + 64 > m.dcap || c.desc_b + 64 > m.hcap) {
-            // growing frees the slot's buffers: let every queued use of them finish
-            hipError_t err = hipStreamSynchronize(ms);
-            if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
-            if (err != hipSuccess) {
-                rc = hip_fail(err, "hipStreamSynchronize");
-                return false;
-            }
-            if ((rc = mslot_reserve(m, e->numa.node, c.desc_at + c.desc_b + 64, c.desc_b + 64))) return false;
-        }
-        // descriptor block (same layout in h and at d + desc_at):
-        //   src u64 | so u64 | dst u64 | oo u64 | len u32 | slot u32   (cnt entries each)
-        uint64_t *h_src = reinterpret_cast<uint64_t *>(m.h);
-        uint64_t *h_so = h_src + cnt, *h_dst = h_so + cnt, *h_oo = h_dst + cnt;
-        uint32_t *h_len = reinterpret_cast<uint32_t *>(h_oo + cnt), *h_slot = h_len + cnt;
-        const unsigned parts = cnt >= 16384 ? pool_of(e)->parts() : 1u;
-        uint64_t psum[64 + 1] = {0};
-        uint8_t same[64];
-        auto range = [&](unsigned p, uint32_t &a0, uint32_t &b0) {
-            a0 = (uint32_t)((uint64_t)cnt * p / parts);
-            b0 = (uint32_t)((uint64_t)cnt * (p + 1) / parts);
-        };
-        pool_of(e)->run(parts, [&](unsigned p) {
-            uint32_t a0, b0;
-            range(p, a0, b0);
-            uint64_t sum = 0;
-            bool eq = true;
-            for (uint32_t q = a0; q < b0; q++) {
-                sum += fr[q].len;
-                eq = eq && fr[q].len == fr[0].len;
-            }
-            psum[p + 1] = sum;
-            same[p] = eq;
-        });
-        c.uniform = true;
-        for (unsigned p = 0; p < parts; p++) {
-            psum[p + 1] += psum[p];
-            c.uniform = c.uniform && same[p];
-        }
-        pool_of(e)->run(parts, [&](unsigned p) {
-            uint32_t a0, b0;
-            range(p, a0, b0);
-            uint64_t io = psum[p], oo = psum[p] + pre * a0;
-            long rs = -1, rd = -1;  // last range hit (frames of one arena: one search each)
-            for (uint32_t q = a0; q < b0; q++) {
-                const fpnn_aes_host_frame &f = fr[q];
-                uint64_t sa = 0, da = 0;
-                if (f.len) {
-                    const uintptr_t x = (uintptr_t)f.src;
-                    if (rs < 0 || x < v.lo[rs] || x + f.len > v.hi[rs]) rs = v.find(f.src, f.len);
-                    sa = (uint64_t)((intptr_t)x + v.delta[rs]);
-                }
-                if (f.len + pre) {
-                    const uintptr_t x = (uintptr_t)f.dst;
-                    if (rd < 0 || x < v.lo[rd] || x + f.len + pre > v.hi[rd]) rd = v.find(f.dst, f.len + pre);
-                    da = (uint64_t)((intptr_t)x + v.delta[rd]);
-                }
-                h_src[q] = sa;
-                h_so[q] = io;
-                h_dst[q] = da;
-                h_oo[q] = oo;
-                h_len[q] = f.len;
-                h_slot[q] = f.key_slot;
-                io += f.len;
-                oo += f.len + pre;
-            }
-        });
-        c.cnt = cnt;
-        si = j;
-        if (hst.on) hst.gather += HostStats::now() - tf;  // (descriptor fill)
-        return true;
-    };
-    // engine stream: chunk t's descriptors H2D; `done` doubles as "descriptors on the device"
-    auto upload = [&](uint64_t t) -> int {
-        const int k = (int)(t % kSlots);
-        MapSlot &m = e->ms[k];
-        HIP_TRY(hipMemcpyAsync(m.d + ch[k].desc_at, m.h, ch[k].desc_b, hipMemcpyHostToDevice, e->stream));
-        HIP_TRY(hipEventRecord(m.done, e->stream));
-        m.busy = true;
-        return FPNN_AES_OK;
-    };
-    int rc = FPNN_AES_OK;
-    if (prepare(0, rc)) rc = upload(0);
-    const MoveJob none{0, nullptr, 0, nullptr, nullptr, 0, 0};
-    for (uint64_t t = 0; rc == FPNN_AES_OK; t++) {
-        const int kt = (int)(t % kSlots), k1 = (int)((t + kSlots - 1) % kSlots), k2 = (int)((t + kSlots - 2) % kSlots);
-        const bool gather_t = ch[kt].cnt != 0;
-        const bool cipher_t1 = t >= 1 && ch[k1].cnt != 0;
-        const bool scatter_t2 = t >= 2 && ch[k2].cnt != 0;
-        if (!gather_t && !cipher_t1 && !scatter_t2) break;
-        // move stream: gather t || scatter t - 2
-        MoveJob gj = none, sj = none, tmp;
-        if (gather_t) {
-            HIP_TRY(hipStreamWaitEvent(ms, e->ms[kt].done, 0));
-            jobs_of(kt, gj, tmp);
-        }
-        if (scatter_t2) {
-            HIP_TRY(hipStreamWaitEvent(ms, e->ms[k2].ciphered, 0));
-            jobs_of(k2, tmp, sj);
-        }
-        HIP_TRY(launch_move_segments(gj, sj, ms));
-        if (gather_t) HIP_TRY(hipEventRecord(e->ms[kt].gathered, ms));
-        // engine stream: cipher t - 1, then upload chunk t + 1 (its slot's previous chunk,
-        // t - 3, was scattered by step t - 1's launch, which the cipher waited for); the
-        // cipher is queued before the host prepares chunk t + 1's descriptors
-        bool next = false, prepared = false;
-        if (cipher_t1) {
-            const Chunk &c = ch[k1];
-            MapSlot &m = e->ms[k1];
-            HIP_TRY(hipStreamWaitEvent(e->stream, m.gathered, 0));
-            MoveJob gq, sq;
-            jobs_of(k1, gq, sq);
-            fpnn_aes_batch bt;
-            memset(&bt, 0, sizeof bt);
-            bt.in = m.d;
-            bt.out = m.d + c.out_at;
-            bt.count = c.cnt;
-            bt.keys = keys;
-            bt.flags = pre ? FPNN_AES_F_WIRE_PREFIX : 0u;
-            if (c.uniform && !pre) {  // dense uniform staging: the K2 / K1d fast paths
-                bt.stride = frames[c.first].len;
-                bt.uniform_len = frames[c.first].len;
-            } else {
-                bt.in_off = gq.doff;
-                bt.out_off = sq.soff;
-                bt.len = gq.len;
-            }
-            if (keys->count > 1) bt.key_slot = gq.len + c.cnt;
-            rc = encrypt ? run_encrypt(e, &bt, nullptr, nullptr, false) : run_decrypt(e, &bt, nullptr, nullptr, false);
-            if (rc) break;
-            HIP_TRY(hipEventRecord(m.ciphered, e->stream));
-        }
-        // host: chunk t + 1's descriptors while the GPU moves and ciphers
-        if (!prepared) next = prepare(t + 1, rc);
-        if (rc) break;
-        // (chunk t + 1 exists only if chunk t - 1 does, for t >= 1: the upload always
-        // follows a cipher; at t = 0 the slot is unused)
-        if (next && (rc = upload(t + 1))) break;
-        if (scatter_t2) ch[k2].cnt = 0;  // (its slot's next chunk is prepared at step t + 1)
-    }
-    const double td = hst.on ? HostStats::now() : 0;
-    HIP_TRY(hipStreamSynchronize(ms));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    if (int rf = stream_idle(e)) rc = rc ? rc : rf;
-    for (auto &m : e->ms) m.busy = false;
-    for (auto &c : ch) c.cnt = 0;
-    *done = si;
-    e->host_path = "host_mapped";
-    if (hst.on)
-        fprintf(stderr, "[fpnn_aes host] mapped %s: %u frames, %.2f ms total, descriptors %.2f, slot waits %.2f, "
-                "final drain %.2f ms, chunk %llu MiB\n", encrypt ? "encrypt" : "decrypt", n,
-                1e3 * (HostStats::now() - t_call), 1e3 * hst.gather, 1e3 * hst.wait, 1e3 * (HostStats::now() - td),
-                (unsigned long long)(kChunk >> 20));
-    return rc;
-}
-
-// Stream-mode host frames that all lie in registered memory: the chunking of host_pipeline
-// (one segment per stream = its frames in array order, round-robin quotas so a chunk
-// advances many chains) with mapped_pipeline's moves: on the move stream one launch per
-// step gathers chunk t's pieces from host memory and scatters chunk t - 2's results to
-// the frames' destinations; the engine stream ciphers chunk t - 1 with the streams'
-// carried (iv, pos) -- chunks in order, so a stream split across chunks continues from
-// the state the previous chunk left -- then uploads chunk t + 1's descriptors.
-// Descriptor block of a chunk: per piece src u64 | so u64 | dst u64 | oo u64 | len u32,
-// then per stream segment off u64 | len u32 | slot u32.
-int mapped_stream_pipeline(fpnn_aes_engine *e, bool encrypt, const fpnn_aes_host_frame *frames, uint32_t n,
-                           const fpnn_aes_keyset *keys, const MapView &v, uint8_t *iv_state, uint32_t *pos_state) {
-    const HostActive active_call(e->device);
-    static const uint64_t kChunk = [] {
-        const char *x = getenv("FPNN_AES_MAP_CHUNK_MB");
-        return (x && atoi(x) > 0 ? (uint64_t)atoi(x) : 32ull) << 20;
-    }();
-    constexpr int kSlots = (int)(sizeof(e->ms) / sizeof(e->ms[0]));
-    // ---- streams in array order (group_streams) ----
-    HostStats hst;
-    const double t_call = hst.on ? HostStats::now() : 0;
-    std::vector<uint32_t> order;
-    std::vector<StreamSeg> segs;
-    group_streams(frames, n, keys->count, order, segs);
-    if (segs.empty()) return FPNN_AES_OK;
-    const uint64_t nseg = segs.size();
-    const double t_sorted = hst.on ? HostStats::now() : 0;
-    DeviceGuard g(e->device);
-    for (auto &m : e->ms)
-        if (int rc = mslot_reserve(m, e->numa.node, 0, 0)) return rc;
-    if (!e->map_stream) HIP_TRY(hipStreamCreateWithFlags(&e->map_stream, hipStreamNonBlocking));
-    hipStream_t ms = e->map_stream;
-    // ---- the streams' (iv, pos), compact, on the device (engine stream) ----
-    if (int rc = sstate_reserve(e, nseg * 20)) return rc;
-    uint8_t *h_state = e->h_sstate, *d_state = e->d_sstate;
-    std::vector<uint64_t> rem(nseg);
-    std::vector<uint32_t> fi(nseg, 0), fo(nseg, 0);
-    uint64_t left = 0;
-    {
-        uint32_t *hp = reinterpret_cast<uint32_t *>(h_state + 16 * nseg);
-        for (uint64_t t = 0; t < nseg; t++) {
-            memcpy(h_state + 16 * t, iv_state + 16ull * segs[t].slot, 16);
-            hp[t] = pos_state[segs[t].slot] & 15u;
-            rem[t] = segs[t].bytes;
-            left += segs[t].bytes;
-        }
-    }
-    HIP_TRY(hipMemcpyAsync(d_state, h_state, nseg * 20, hipMemcpyHostToDevice, e->stream));
-    // Chunks of kChunk bytes (as the package path: the moves of chunk t overlap the cipher
-    // of chunk t - 1, so more, smaller chunks pipeline better than a few large ones), each
-    // taking a quota from as many streams as fit: the encrypt of a chunk is one serial CFB
-    // chain per stream, so its parallelism is the number of streams it spans.
-    const uint64_t chunk = kChunk;
-    const uint64_t quota = std::max<uint64_t>(1024, (chunk / nseg + 15) & ~15ull);
-    // the move stream starts after work already queued on the engine stream
-    HIP_TRY(hipEventRecord(e->ms[0].ciphered, e->stream));
-    HIP_TRY(hipStreamWaitEvent(ms, e->ms[0].ciphered, 0));
-    struct Chunk {
-        uint32_t np = 0, ns = 0;  // pieces, stream segments (np = 0: no chunk in the slot)
-        uint32_t uni = 0;         // every segment this many bytes (0: ragged)
-        uint64_t state0 = 0, out_at = 0, desc_at = 0, desc_b = 0;
-    } ch[kSlots];
-    uint64_t next = 0;  // round-robin cursor over segs
-    auto jobs_of = [&](int slot, MoveJob &gather, MoveJob &scatter) {
-        const Chunk &c = ch[slot];
-        MapSlot &m = e->ms[slot];
-        const uint64_t *d_src = reinterpret_cast<const uint64_t *>(m.d + c.desc_at);
-        const uint64_t *d_so = d_src + c.np, *d_dst = d_so + c.np, *d_oo = d_dst + c.np;
-        const uint32_t *d_len = reinterpret_cast<const uint32_t *>(d_oo + c.np);
-        gather = MoveJob{0, d_src, (uint64_t)(uintptr_t)m.d, d_so, d_len, 0, c.np};
-        scatter = MoveJob{(uint64_t)(uintptr_t)(m.d + c.out_at), d_oo, 0, d_dst, d_len, 0, c.np};
-    };
-    auto seg_arrays = [&](int slot, const uint64_t *&off, const uint32_t *&len, const uint32_t *&sl) {
-        const Chunk &c = ch[slot];
-        const uint8_t *base = e->ms[slot].d + c.desc_at + (uint64_t)c.np * 36;
-        const uint64_t a = ((uint64_t)(uintptr_t)base + 7) & ~7ull;
-        off = reinterpret_cast<const uint64_t *>(a);
-        len = reinterpret_cast<const uint32_t *>(off + c.ns);
-        sl = len + c.ns;
-    };
-    // host: chunk t's pieces and descriptors into its slot's pinned block
-    auto prepare = [&](uint64_t t, int &rc) -> bool {
-        const int k = (int)(t % kSlots);
-        Chunk &c = ch[k];
-        c.np = c.ns = 0;
-        if (left == 0) return false;
-        MapSlot &m = e->ms[k];
-        if (m.busy) {
-            const double tw = hst.on ? HostStats::now() : 0;
-            if (hipError_t err = hipEventSynchronize(m.done)) {
-                rc = hip_fail(err, "hipEventSynchronize");
-                return false;
-            }
-            if (hst.on) hst.wait += HostStats::now() - tw;
-            m.busy = false;
-        }
-        const double tf = hst.on ? HostStats::now() : 0;
-        std::vector<Piece> pieces;
-        struct CS {
-            uint32_t slot;
-            uint64_t at, len;
-        };
-        std::vector<CS> cs;
-        uint64_t s = next < nseg ? next : 0;
-        while (rem[s] == 0) s = s + 1 < nseg ? s + 1 : 0;  // left > 0: terminates
-        c.state0 = s;
-        uint64_t in_b = 0;
-        for (; s < nseg && in_b < chunk; s++) {
-            const StreamSeg &sg = segs[s];
-            const uint64_t take = std::min(rem[s], quota);
-            uint64_t took = 0;
-            while (took < take) {
-                const uint32_t fidx = order[sg.first + fi[s]];
-                const fpnn_aes_host_frame &f = frames[fidx];
-                const uint32_t part = (uint32_t)std::min<uint64_t>(f.len - fo[s], take - took);
-                if (part) pieces.push_back({fidx, fo[s], part});
-                took += part;
-                fo[s] += part;
-                if (fo[s] == f.len) {
-                    fi[s]++;
-                    fo[s] = 0;
-                }
-            }
-            cs.push_back({sg.slot, in_b, take});
-            rem[s] -= take;
-            left -= take;
-            in_b += take;
-        }
-        next = s;
-        const uint32_t np = (uint32_t)pieces.size(), ns = (uint32_t)cs.size();
-        const uint64_t in_pad = (in_b + 255) & ~255ull;
-        c.out_at = in_pad;
-        c.desc_at = 2 * in_pad;
-        c.desc_b = (uint64_t)np * 36 + 8 + (uint64_t)ns * 16;
-        if (c.desc_at + c.desc_b + 64 > m.dcap || c.desc_b + 64 > m.hcap) {
-            hipError_t err = hipStreamSynchronize(ms);  // growing frees the slot's buffers
-            if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
-            if (err != hipSuccess) {
-                rc = hip_fail(err, "hipStreamSynchronize");
-                return false;
-            }
-            if ((rc = mslot_reserve(m, e->numa.node, c.desc_at + c.desc_b + 64, c.desc_b + 64))) return false;
-        }
-        uint64_t *h_src = reinterpret_cast<uint64_t *>(m.h);
-        uint64_t *h_so = h_src + np, *h_dst = h_so + np, *h_oo = h_dst + np;
-        uint32_t *h_len = reinterpret_cast<uint32_t *>(h_oo + np);
-        const unsigned parts = np >= 16384 ? pool_of(e)->parts() : 1u;
-        std::vector<uint64_t> at(np);
-        {
-            uint64_t a = 0;
-            for (uint32_t q = 0; q < np; q++) {
-                at[q] = a;
-                a += pieces[q].len;
-            }
-        }
-        pool_of(e)->run(parts, [&](unsigned p) {
-            const uint32_t a0 = (uint32_t)((uint64_t)np * p / parts), b0 = (uint32_t)((uint64_t)np * (p + 1) / parts);
-            long rs = -1, rd = -1;
-            for (uint32_t q = a0; q < b0; q++) {
-                const Piece &pc = pieces[q];
-                const fpnn_aes_host_frame &f = frames[pc.frame];
-                const uintptr_t xs = (uintptr_t)f.src + pc.off, xd = (uintptr_t)f.dst + pc.off;
-                if (rs < 0 || xs < v.lo[rs] || xs + pc.len > v.hi[rs]) rs = v.find((const void *)xs, pc.len);
-                if (rd < 0 || xd < v.lo[rd] || xd + pc.len > v.hi[rd]) rd = v.find((const void *)xd, pc.len);
-                h_src[q] = (uint64_t)((intptr_t)xs + v.delta[rs]);
-                h_so[q] = at[q];
-                h_dst[q] = (uint64_t)((intptr_t)xd + v.delta[rd]);
-                h_oo[q] = at[q];
-                h_len[q] = pc.len;
-            }
-        });
-        const uint64_t sa = (((uint64_t)(uintptr_t)(m.h + (uint64_t)np * 36)) + 7) & ~7ull;
-        uint64_t *h_off = reinterpret_cast<uint64_t *>(sa);
-        uint32_t *h_slen = reinterpret_cast<uint32_t *>(h_off + ns), *h_sslot = h_slen + ns;
-        for (uint32_t q = 0; q < ns; q++) {
-            h_off[q] = cs[q].at;
-            h_slen[q] = (uint32_t)cs[q].len;
-            h_sslot[q] = cs[q].slot;
-        }
-        c.np = np;
-        c.ns = ns;
-        c.uni = (uint32_t)cs[0].len;  // (segments lie back to back: equal lengths = a stride)
-        for (uint32_t q = 1; q < ns && c.uni; q++)
-            if (cs[q].len != c.uni) c.uni = 0;
-        if (hst.on) hst.gather += HostStats::now() - tf;
-        return true;
-    };
-    auto upload = [&](uint64_t t) -> int {
-        const int k = (int)(t % kSlots);
-        MapSlot &m = e->ms[k];
-        HIP_TRY(hipMemcpyAsync(m.d + ch[k].desc_at, m.h, ch[k].desc_b, hipMemcpyHostToDevice, e->stream));
-        HIP_TRY(hipEventRecord(m.done, e->stream));
-        m.busy = true;
-        return FPNN_AES_OK;
-    };
-    int rc = FPNN_AES_OK;
-    if (prepare(0, rc)) rc = upload(0);
-    const MoveJob none{0, nullptr, 0, nullptr, nullptr, 0, 0};
-    for (uint64_t t = 0; rc == FPNN_AES_OK; t++) {
-        const int kt = (int)(t % kSlots), k1 = (int)((t + kSlots - 1) % kSlots), k2 = (int)((t + kSlots - 2) % kSlots);
-        const bool gather_t = ch[kt].np != 0;
-        const bool cipher_t1 = t >= 1 && ch[k1].np != 0;
-        const bool scatter_t2 = t >= 2 && ch[k2].np != 0;
-        if (!gather_t && !cipher_t1 && !scatter_t2) break;
-        MoveJob gj = none, sj = none, tmp;
-        if (gather_t) {
-            HIP_TRY(hipStreamWaitEvent(ms, e->ms[kt].done, 0));
-            jobs_of(kt, gj, tmp);
-        }
-        if (scatter_t2) {
-            HIP_TRY(hipStreamWaitEvent(ms, e->ms[k2].ciphered, 0));
-            jobs_of(k2, tmp, sj);
-        }
-        HIP_TRY(launch_move_segments(gj, sj, ms));
-        if (gather_t) HIP_TRY(hipEventRecord(e->ms[kt].gathered, ms));
-        // the cipher of chunk t - 1 is queued before the host prepares chunk t + 1 (the
-        // engine stream is not left empty while the host works)
-        bool more = false, prepared = false;
-        if (cipher_t1) {
-            const Chunk &c = ch[k1];
-            MapSlot &m = e->ms[k1];
-            HIP_TRY(hipStreamWaitEvent(e->stream, m.gathered, 0));
-            const uint64_t *off;
-            const uint32_t *len, *sl;
-            seg_arrays(k1, off, len, sl);
-            fpnn_aes_batch bt;
-            memset(&bt, 0, sizeof bt);
-            bt.in = m.d;
-            bt.out = m.d + c.out_at;
-            bt.count = c.ns;
-            if (encrypt && c.uni) {
-                // every stream takes the same quota (S1's middle chunks): a uniform batch,
-                // so the encrypt skips the ragged length ordering (its bucket counters see
-                // one length: 16 384 atomics on one word, ~1 ms per chunk in the r04q trace)
-                bt.stride = c.uni;
-                bt.uniform_len = c.uni;
-            } else {
-                bt.in_off = off;
-                bt.len = len;
-            }
-            bt.key_slot = keys->count > 1 ? sl : nullptr;
-            bt.keys = keys;
-            uint8_t *ivp = d_state + 16 * c.state0;
-            uint32_t *posp = reinterpret_cast<uint32_t *>(d_state + 16 * nseg) + c.state0;
-            rc = encrypt ? run_encrypt(e, &bt, ivp, posp, true) : run_decrypt(e, &bt, ivp, posp, true);
-            if (rc) break;
-            HIP_TRY(hipEventRecord(m.ciphered, e->stream));
-        }
-        if (!prepared) more = prepare(t + 1, rc);
-        if (rc) break;
-        if (more && (rc = upload(t + 1))) break;
-        if (scatter_t2) ch[k2].np = 0;
-    }
-    const double td = hst.on ? HostStats::now() : 0;
-    HIP_TRY(hipStreamSynchronize(ms));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    if (int rf = stream_idle(e)) rc = rc ? rc : rf;
-    for (auto &m : e->ms) m.busy = false;
-    for (auto &c : ch) c.np = 0;
-    if (!rc) {
-        HIP_TRY(hipMemcpy(h_state, d_state, nseg * 20, hipMemcpyDeviceToHost));
-        const uint32_t *hp = reinterpret_cast<const uint32_t *>(h_state + 16 * nseg);
-        for (uint64_t t = 0; t < nseg; t++) {
-            memcpy(iv_state + 16ull * segs[t].slot, h_state + 16 * t, 16);
-            pos_state[segs[t].slot] = hp[t];
-        }
-    }
-    e->host_path = "host_mapped";
-    if (hst.on)
-        fprintf(stderr, "[fpnn_aes host] mapped stream %s: %u frames, %llu streams, %.2f ms total, sort %.2f, "
-                "descriptors %.2f, slot waits %.2f, final drain %.2f ms\n", encrypt ? "encrypt" : "decrypt", n,
-                (unsigned long long)nseg, 1e3 * (HostStats::now() - t_call), 1e3 * (t_sorted - t_call),
-                1e3 * hst.gather, 1e3 * hst.wait, 1e3 * (HostStats::now() - td));
-    return rc;
-}
-
-// every frame of the call (source and destination) inside registered memory
-bool all_mapped(const fpnn_aes_engine *e, const fpnn_aes_host_frame *frames, uint32_t n, const MapView &v) {
-    std::atomic<bool> ok{true};
-    const unsigned parts = n >= 16384 ? pool_of(const_cast<fpnn_aes_engine *>(e))->parts() : 1u;
-    pool_of(const_cast<fpnn_aes_engine *>(e))->run(parts, [&](unsigned p) {
-        const uint32_t a0 = (uint32_t)((uint64_t)n * p / parts), b0 = (uint32_t)((uint64_t)n * (p + 1) / parts);
-        long rs = -1, rd = -1;
-        for (uint32_t q = a0; q < b0 && ok.load(std::memory_order_relaxed); q++) {
-            const fpnn_aes_host_frame &f = frames[q];
-            if (!f.len) continue;
-            const uintptr_t xs = (uintptr_t)f.src, xd = (uintptr_t)f.dst;
-            if ((rs < 0 || xs < v.lo[rs] || xs + f.len > v.hi[rs]) && (rs = v.find(f.src, f.len)) < 0) ok = false;
-            if ((rd < 0 || xd < v.lo[rd] || xd + f.len > v.hi[rd]) && (rd = v.find(f.dst, f.len)) < 0) ok = false;
-        }
-    });
-    return ok.load();
-}
-
-bool mapped_enabled() {
-    const char *v = getenv("FPNN_AES_HOST_MAPPED");
-    return !v || atoi(v) != 0;
-}
-
-}  // namespace
-
-int fpnn_aes_package_host(fpnn_aes_engine *e, int encrypt, const fpnn_aes_host_frame *frames, uint32_t n,
-                          const fpnn_aes_keyset *keys, uint32_t flags) {
-    if (int rc = check_host_frames(e, frames, n, keys)) return rc;
-    if (int rc = debug_fail_point()) return rc;
-    if (!encrypt && (flags & FPNN_AES_F_WIRE_PREFIX)) return FPNN_AES_ERR_ARG;
-    if (flags & FPNN_AES_F_WIRE_PREFIX)
-        for (uint32_t i = 0; i < n; i++)
-            if (!frames[i].dst) return FPNN_AES_ERR_ARG;
-    if (!n) return FPNN_AES_OK;
-    if (mapped_enabled()) {  // every frame in registered host memory: the GPU moves the bytes
-        MapView v;
-        if (int rc = map_view(e->device, v)) return rc;
-        const uint64_t pre = (flags & FPNN_AES_F_WIRE_PREFIX) ? 4 : 0;
-        if (!v.lo.empty() && (!frames[0].len || v.find(frames[0].src, frames[0].len) >= 0) &&
-            (!(frames[0].len + pre) || v.find(frames[0].dst, frames[0].len + pre) >= 0)) {
-            // frames in registered memory from the first on: mapped until the first frame
-            // that is not, the rest (if any) staged -- package frames are independent
-            uint32_t done = 0;
-            if (int rc = mapped_pipeline(e, encrypt != 0, frames, n, keys, flags, v, &done)) return rc;
-            if (done == n) return FPNN_AES_OK;
-            frames += done;
-            n -= done;
-            const int rc = host_pipeline(e, encrypt != 0, false, frames, n, keys, flags, nullptr, nullptr);
-            if (done) e->host_path = "host_mapped+staged";
-            return rc;
-        }
-    }
-    return host_pipeline(e, encrypt != 0, false, frames, n, keys, flags, nullptr, nullptr);
-}
-
-int fpnn_aes_host_register(void *ptr, size_t len) {
-    if (!ptr || !len) return FPNN_AES_ERR_ARG;
-    const uintptr_t lo = (uintptr_t)ptr, hi = lo + len;
-    if (hi < lo) return FPNN_AES_ERR_ARG;
-    std::lock_guard<std::mutex> lk(g_map_mu);
-    auto it = std::lower_bound(g_mapped.begin(), g_mapped.end(), lo,
-                               [](const MappedRange &r, uintptr_t x) { return r.lo < x; });
-    if ((it != g_mapped.end() && it->lo < hi) || (it != g_mapped.begin() && std::prev(it)->hi > lo)) {
-        g_last_error = "fpnn_aes_host_register: range overlaps a registered range";
-        return FPNN_AES_ERR_ARG;
-    }
-    HIP_TRY(hipHostRegister(ptr, len, hipHostRegisterPortable | hipHostRegisterMapped));
-    MappedRange r;
-    r.lo = lo;
-    r.hi = hi;
-    for (auto &d : r.delta) d = INTPTR_MIN;
-    g_mapped.insert(it, r);
-    return FPNN_AES_OK;
-}
-
-int fpnn_aes_host_unregister(void *ptr) {
-    std::lock_guard<std::mutex> lk(g_map_mu);
-    auto it = std::find_if(g_mapped.begin(), g_mapped.end(), [ptr](const MappedRange &r) { return r.lo == (uintptr_t)ptr; });
-    if (it == g_mapped.end()) return FPNN_AES_ERR_ARG;
-    g_mapped.erase(it);
-    HIP_TRY(hipHostUnregister(ptr));
-    return FPNN_AES_OK;
-}
-
-int fpnn_aes_host_is_mapped(const void *ptr, size_t len) {
-    std::lock_guard<std::mutex> lk(g_map_mu);
-    const uintptr_t p = (uintptr_t)ptr;
-    for (const auto &r : g_mapped)
-        if (p >= r.lo && p + len <= r.hi && p + len >= p) return 1;
-    return 0;
-}
-
-int fpnn_aes_stream_host(fpnn_aes_engine *e, int encrypt, const fpnn_aes_host_frame *frames, uint32_t n,
-                         const fpnn_aes_keyset *keys, uint8_t *iv_state, uint32_t *pos_state) {
-    if (int rc = check_host_frames(e, frames, n, keys)) return rc;
-    if (int rc = debug_fail_point()) return rc;
-    if (n && (!iv_state || !pos_state)) return FPNN_AES_ERR_ARG;
-    if (!n) return FPNN_AES_OK;
-    if (mapped_enabled()) {  // every frame in registered host memory: the GPU moves the bytes
-        MapView v;
-        if (int rc = map_view(e->device, v)) return rc;
-        if (!v.lo.empty() && all_mapped(e, frames, n, v))
-            return mapped_stream_pipeline(e, encrypt != 0, frames, n, keys, v, iv_state, pos_state);
-    }
-    return host_pipeline(e, encrypt != 0, true, frames, n, keys, 0, iv_state, pos_state);
-}
-
-// ---- one host batch over several engines (GPUs) ------------------------------------------
-// Each engine runs its share through its own host_pipeline in its own thread (engine 0's in
-// the caller's), on that engine's NUMA node; errors are collected and the first one (by
-// engine index) is returned, with its message.
-static int run_multi(fpnn_aes_engine *const *engines, int n_engines, const std::function<int(int)> &fn) {
-    std::vector<int> rc(n_engines, FPNN_AES_OK);
-    std::vector<std::string> msg(n_engines);
-    std::vector<std::thread> th;
-    for (int k = 1; k < n_engines; k++)
-        th.emplace_back([&, k] {
-            (void)fpnn_aes::numa_pin_thread(engines[k]->numa);
-            rc[k] = fn(k);
-            if (rc[k]) msg[k] = g_last_error;
-        });
-    rc[0] = fn(0);
-    if (rc[0]) msg[0] = g_last_error;
-    for (auto &t : th) t.join();
-    for (int k = 0; k < n_engines; k++)
-        if (rc[k]) {
-            g_last_error = "engine " + std::to_string(k) + ": " + msg[k];
-            return rc[k];
-        }
-    return FPNN_AES_OK;
-}
-
-int fpnn_aes_package_host_multi(fpnn_aes_engine *const *engines, const fpnn_aes_keyset *const *keys, int n_engines,
-                                int encrypt, const fpnn_aes_host_frame *frames, uint32_t n, uint32_t flags) {
-    if (!engines || !keys || n_engines < 1 || (n && !frames)) return FPNN_AES_ERR_ARG;
-    for (int k = 0; k < n_engines; k++)
-        if (!engines[k] || !keys[k] || keys[k]->count != keys[0]->count || keys[k]->nrounds != keys[0]->nrounds)
-            return FPNN_AES_ERR_ARG;
-    if (n_engines == 1 || n < 2) return fpnn_aes_package_host(engines[0], encrypt, frames, n, keys[0], flags);
-    // byte-balanced contiguous ranges of frames
-    uint64_t total = 0;
-    for (uint32_t i = 0; i < n; i++) total += frames[i].len;
-    std::vector<uint32_t> cut(n_engines + 1, n);
-    cut[0] = 0;
-    uint64_t acc = 0;
-    int p = 1;
-    for (uint32_t i = 0; i < n && p < n_engines; i++) {
-        acc += frames[i].len;
-        while (p < n_engines && acc * n_engines >= total * p) cut[p++] = i + 1;
-    }
-    return run_multi(engines, n_engines, [&](int k) {
-        return fpnn_aes_package_host(engines[k], encrypt, frames + cut[k], cut[k + 1] - cut[k], keys[k], flags);
-    });
-}
-
-int fpnn_aes_stream_host_multi(fpnn_aes_engine *const *engines, const fpnn_aes_keyset *const *keys, int n_engines,
-                               int encrypt, const fpnn_aes_host_frame *frames, uint32_t n, uint8_t *iv_state,
-                               uint32_t *pos_state) {
-    if (!engines || !keys || n_engines < 1 || (n && (!frames || !iv_state || !pos_state))) return FPNN_AES_ERR_ARG;
-    for (int k = 0; k < n_engines; k++)
-        if (!engines[k] || !keys[k] || keys[k]->count != keys[0]->count || keys[k]->nrounds != keys[0]->nrounds)
-            return FPNN_AES_ERR_ARG;
-    if (n_engines == 1 || n < 2)
-        return fpnn_aes_stream_host(engines[0], encrypt, frames, n, keys[0], iv_state, pos_state);
-    // whole streams to engines, longest first onto the least-loaded engine (a stream's frames
-    // stay in order on one engine: its CFB state chains through them)
-    std::unordered_map<uint32_t, uint64_t> bytes;
-    for (uint32_t i = 0; i < n; i++) bytes[frames[i].key_slot] += frames[i].len;
-    std::vector<std::pair<uint64_t, uint32_t>> order;
-    order.reserve(bytes.size());
-    for (const auto &kv : bytes) order.push_back({kv.second, kv.first});
-    std::sort(order.begin(), order.end(), [](const std::pair<uint64_t, uint32_t> &a,
-                                             const std::pair<uint64_t, uint32_t> &b) {
-        return a.first != b.first ? a.first > b.first : a.second < b.second;
-    });
-    std::vector<uint64_t> load(n_engines, 0);
-    std::unordered_map<uint32_t, int> owner;
-    for (const auto &o : order) {
-        const int k = (int)(std::min_element(load.begin(), load.end()) - load.begin());
-        owner[o.second] = k;
-        load[k] += o.first;
-    }
-    std::vector<std::vector<fpnn_aes_host_frame>> part(n_engines);
-    for (uint32_t i = 0; i < n; i++) part[owner[frames[i].key_slot]].push_back(frames[i]);
-    return run_multi(engines, n_engines, [&](int k) {
-        return fpnn_aes_stream_host(engines[k], encrypt, part[k].data(), (uint32_t)part[k].size(), keys[k], iv_state,
-                                    pos_state);
-    });
 }
 
 int fpnn_aes_device_alloc(fpnn_aes_engine *e, size_t bytes, void **out) {
