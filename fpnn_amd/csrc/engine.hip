@@ -28,11 +28,14 @@ const uint8_t *isbox_of(const fpnn_aes_engine *e) { return e->d_tables + 2304; }
 // capacity of its own until it grows)
 uint32_t table_slots(const fpnn_aes_keyset *ks) { return std::max(ks->capacity, ks->count); }
 
-// a grow()-managed buffer at engine teardown (the stream is idle)
-void release_scratch(fpnn_aes_engine *e, void *p) {
-    if (!p) return;
-    if (e->pools) (void)hipFreeAsync(p, e->stream);
-    else (void)hipFree(p);
+// the smallest power-of-two workgroup (at least one wave) that still spreads `lanes` over
+// every CU, and its grid: at most one workgroup per CU (further work grid-strides)
+struct Spread { int threads, grid; };
+Spread spread_over_cus(const fpnn_aes_engine *e, uint64_t lanes) {
+    int threads = 64;
+    while (threads < kThreads && (uint64_t)threads * e->num_cus < lanes) threads *= 2;
+    const uint64_t want = (lanes + threads - 1) / threads;
+    return {threads, (int)(want < (uint64_t)e->num_cus ? (want ? want : 1) : (uint64_t)e->num_cus)};
 }
 
 void free_deferred(fpnn_aes_engine *e) {  // the engine's stream is idle
@@ -48,8 +51,8 @@ int fpnn_aes::stream_idle(fpnn_aes_engine *e) {
     free_deferred(e);
     const uint32_t f = e->h_fault ? __atomic_exchange_n(e->h_fault, 0u, __ATOMIC_ACQ_REL) : 0u;
     if (!f) return FPNN_AES_OK;
-    if ((f & kFaultLengthOrder) && e->d_buckets)  // start the next ragged call from a zero block
-        (void)hipMemsetAsync(e->d_buckets, 0, e->cap_buckets * sizeof(uint32_t), e->stream);
+    if ((f & kFaultLengthOrder) && e->buckets.p)  // start the next ragged call from a zero block
+        (void)hipMemsetAsync(e->buckets.p, 0, e->buckets.cap * sizeof(uint32_t), e->stream);
     g_last_error = (f & kFaultLookback)      ? "block map: a look-back gave up waiting for a tile (results of that call invalid)"
                    : (f & kFaultLengthOrder) ? "length order: bucket counts did not add up to the batch (results of that call invalid)"
                    : (f & kFaultFrameTable)  ? "first_frame: not non-decreasing from 0 to count (results of that call invalid)"
@@ -137,13 +140,41 @@ KBatch make_kbatch(const fpnn_aes_engine *e, const fpnn_aes_batch *b, uint8_t *i
     return k;
 }
 
+// DevKey of a host schedule (rijndael_context layout, big-endian rk words) and, where given,
+// the slot's IV
+void devkey_from_schedule(DevKey *hk, const fpnn_aes_schedule *ctx, const uint8_t *iv = nullptr) {
+    memset(hk, 0, sizeof *hk);
+    for (int k = 0; k < 4 * (ctx->nrounds + 1); k++) hk->rk[k] = bswap32(ctx->rk[k]);
+    hk->nrounds = (uint32_t)ctx->nrounds;
+    hk->keylen = (uint32_t)(ctx->nrounds - 6) * 4;
+    if (iv) memcpy(hk->iv, iv, 16);
+}
+
 bool is_uniform_layout(const fpnn_aes_batch *b) {
     return !b->in_off && !b->out_off && !b->len && !b->key_slot;
 }
 
-
 #ifdef FPNN_AES_BOUNDS
 // ---- the address-audit build (audit.hpp, `make audit`) ----------------------------------
+// One call's extent table, built on the host: set() names a buffer's bytes (a null buffer is
+// not checked), publish() puts the table on the device once the stream is drained.
+struct AuditExtents {
+    AuditTable t;
+    AuditExtents() { memset(&t, 0, sizeof t); }
+    void set(AuditBuf i, const void *p, uint64_t bytes) {
+        if (!p) return;
+        t.lo[i] = (uint64_t)(uintptr_t)p;
+        t.hi[i] = t.lo[i] + bytes;
+    }
+    int publish(fpnn_aes_engine *e, AuditTable **aud) {
+        if (!e->d_aud) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->d_aud), sizeof(AuditTable)));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        HIP_TRY(hipMemcpy(e->d_aud, &t, sizeof t, hipMemcpyHostToDevice));
+        *aud = e->d_aud;
+        return FPNN_AES_OK;
+    }
+};
+
 // Before an encrypt call: the extents of every buffer the call's kernels may touch, in the
 // engine's table (synchronous; the audit build is a checker, not a product).  The scratch
 // the call grows is grown here first so that its extent is known.
@@ -152,43 +183,30 @@ bool is_uniform_layout(const fpnn_aes_batch *b) {
 // per-segment slot scratch are registered (the latter also as key_slot: K1r's view of it).
 int audit_begin(fpnn_aes_engine *e, const fpnn_aes_batch *b, const uint8_t *iv_state, const uint32_t *pos_state,
                 KBatch &k, const FrameTable *frames = nullptr) {
-    int rc;
-    if (!e->d_aud) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->d_aud), sizeof(AuditTable)));
-    if ((rc = grow(e, e->d_perm, e->cap_perm, b->count))) return rc;
-    if ((rc = grow(e, e->d_sink, e->cap_sink, 2ull * e->num_cus * (kThreads / 64)))) return rc;
-    if (kLengthOrderWords > e->cap_buckets) {
-        if ((rc = grow(e, e->d_buckets, e->cap_buckets, kLengthOrderWords))) return rc;
-        HIP_TRY(hipMemsetAsync(e->d_buckets, 0, e->cap_buckets * sizeof(uint32_t), e->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    AuditTable t;
-    memset(&t, 0, sizeof t);
     const uint64_t n = b->count;
-    auto set = [&](AuditBuf i, const void *p, uint64_t bytes) {
-        if (!p) return;
-        t.lo[i] = (uint64_t)(uintptr_t)p;
-        t.hi[i] = t.lo[i] + bytes;
-    };
-    set(AB_IN_OFF, b->in_off, 8 * n);
-    set(AB_OUT_OFF, b->out_off, 8 * n);
-    set(AB_LEN, b->len, 4 * n);
-    set(AB_SLOT, b->key_slot, 4 * n);
+    if (int rc = scratch_ensure(e, need_encrypt_ragged(scratch_shape(e), n, true))) return rc;
+    HIP_TRY(hipStreamSynchronize(e->stream));  // (the descriptor arrays are read below)
+    AuditExtents x;
+    x.set(AB_IN_OFF, b->in_off, 8 * n);
+    x.set(AB_OUT_OFF, b->out_off, 8 * n);
+    x.set(AB_LEN, b->len, 4 * n);
+    x.set(AB_SLOT, b->key_slot, 4 * n);
     const uint64_t slots = std::max<uint64_t>(b->keys->count, b->keys->capacity);
-    set(AB_KEYS, b->keys->d_keys, sizeof(DevKey) * slots);
-    set(AB_EIV, b->keys->d_eiv, 16 * slots);
+    x.set(AB_KEYS, b->keys->d_keys, sizeof(DevKey) * slots);
+    x.set(AB_EIV, b->keys->d_eiv, 16 * slots);
     const uint64_t nstate = !frames ? n : frames->state_slot ? frames->slot_bound : frames->nstreams;
-    set(AB_IV_STATE, iv_state, 16 * nstate);
-    set(AB_POS_STATE, pos_state, 4 * nstate);
-    set(AB_POS_SNAP, pos_state, 4 * nstate);
-    if (frames) set(AB_FIRST_FRAME, frames->first_frame, 4 * ((uint64_t)frames->nstreams + 1));
+    x.set(AB_IV_STATE, iv_state, 16 * nstate);
+    x.set(AB_POS_STATE, pos_state, 4 * nstate);
+    x.set(AB_POS_SNAP, pos_state, 4 * nstate);
+    if (frames) x.set(AB_FIRST_FRAME, frames->first_frame, 4 * ((uint64_t)frames->nstreams + 1));
     if (frames && frames->state_slot) {
-        set(AB_STATE_SLOT, frames->state_slot, 4 * (uint64_t)frames->nstreams);
-        set(AB_SEG_SLOT, frames->seg_slot, 4 * n);
-        set(AB_SLOT, frames->seg_slot, 4 * n);
+        x.set(AB_STATE_SLOT, frames->state_slot, 4 * (uint64_t)frames->nstreams);
+        x.set(AB_SEG_SLOT, frames->seg_slot, 4 * n);
+        x.set(AB_SLOT, frames->seg_slot, 4 * n);
     }
-    set(AB_PERM, e->d_perm, 4 * n);
-    set(AB_SINK, e->d_sink, 16 * e->cap_sink);
-    set(AB_BLOCK, e->d_buckets, 4 * (uint64_t)kLengthOrderWords);
+    x.set(AB_PERM, e->perm.p, 4 * n);
+    x.set(AB_SINK, e->sink.p, 16 * e->sink.cap);
+    x.set(AB_BLOCK, e->buckets.p, 4 * (uint64_t)kLengthOrderWords);
     // the payload: the union of the segments' byte ranges (the kernels also check each
     // access against its own segment)
     std::vector<uint64_t> io(n), oo(n);
@@ -211,16 +229,29 @@ int audit_begin(fpnn_aes_engine *e, const fpnn_aes_batch *b, const uint8_t *iv_s
             ohi = std::max(ohi, oo[i] + ln[i] + wire);
         }
     }
-    if (ihi) set(AB_IN, b->in + ilo, ihi - ilo);
-    else set(AB_IN, b->in, 1);  // (nothing may be read)
-    if (ohi) set(AB_OUT, b->out + olo, ohi - olo);
-    else set(AB_OUT, b->out, 1);
+    if (ihi) x.set(AB_IN, b->in + ilo, ihi - ilo);
+    else x.set(AB_IN, b->in, 1);  // (nothing may be read)
+    if (ohi) x.set(AB_OUT, b->out + olo, ohi - olo);
+    else x.set(AB_OUT, b->out, 1);
     // (the audit's own test: an `out` extent this many bytes short must be reported)
     if (const char *v = getenv("FPNN_AES_AUDIT_SHRINK_OUT"))
-        if (t.hi[AB_OUT] > t.lo[AB_OUT] + (uint64_t)atoll(v)) t.hi[AB_OUT] -= (uint64_t)atoll(v);
-    HIP_TRY(hipMemcpy(e->d_aud, &t, sizeof t, hipMemcpyHostToDevice));
-    k.aud = e->d_aud;
-    return FPNN_AES_OK;
+        if (x.t.hi[AB_OUT] > x.t.lo[AB_OUT] + (uint64_t)atoll(v)) x.t.hi[AB_OUT] -= (uint64_t)atoll(v);
+    return x.publish(e, &k.aud);
+}
+
+// a key-table or stream-state write (k_keytable.hip): the table and the caller's arrays
+int audit_begin_keytable(fpnn_aes_engine *e, const fpnn_aes_keyset *ks, KeyTableArgs &a) {
+    AuditExtents x;
+    const uint64_t slots = table_slots(ks);
+    x.set(AB_KEYS, a.keys, sizeof(DevKey) * slots);
+    x.set(AB_EIV, a.eiv, 16 * slots);
+    x.set(AB_KT_SLOTS, a.slots, 4 * (uint64_t)a.count);
+    x.set(AB_KT_RAW, a.raw, (uint64_t)ks->keylen * a.count);
+    x.set(AB_KT_IVS, a.ivs, 16 * (uint64_t)a.count);
+    x.set(AB_KT_OK, a.ok, a.count);
+    x.set(AB_IV_STATE, a.iv_state, 16 * (uint64_t)a.slot_bound);
+    x.set(AB_POS_STATE, a.pos_state, 4 * (uint64_t)a.slot_bound);
+    return x.publish(e, &a.aud);
 }
 
 const char *audit_buf_name(uint32_t i) {
@@ -249,17 +280,14 @@ int audit_end(fpnn_aes_engine *e, int rc) {
     fprintf(stderr, "[fpnn_aes audit] %s\n", buf);
     return FPNN_AES_ERR_DEVICE;
 }
-#endif
-
-int run_encrypt_calls(fpnn_aes_engine *e, const fpnn_aes_batch *b, uint8_t *iv_state, uint32_t *pos_state, bool stream);
-
-int run_encrypt(fpnn_aes_engine *e, const fpnn_aes_batch *b, uint8_t *iv_state, uint32_t *pos_state, bool stream) {
-#ifdef FPNN_AES_BOUNDS
-    return audit_end(e, run_encrypt_calls(e, b, iv_state, pos_state, stream));
-#else
-    return run_encrypt_calls(e, b, iv_state, pos_state, stream);
-#endif
+#else  // the product build: no table, and audit_end(e, rc) is rc
+inline int audit_begin(fpnn_aes_engine *, const fpnn_aes_batch *, const uint8_t *, const uint32_t *, KBatch &,
+                       const FrameTable * = nullptr) {
+    return FPNN_AES_OK;
 }
+inline int audit_begin_keytable(fpnn_aes_engine *, const fpnn_aes_keyset *, KeyTableArgs &) { return FPNN_AES_OK; }
+inline int audit_end(fpnn_aes_engine *, int rc) { return rc; }
+#endif
 
 int run_encrypt_calls(fpnn_aes_engine *e, const fpnn_aes_batch *b, uint8_t *iv_state, uint32_t *pos_state, bool stream) {
     int rc = check_batch(e, b);
@@ -271,9 +299,7 @@ int run_encrypt_calls(fpnn_aes_engine *e, const fpnn_aes_batch *b, uint8_t *iv_s
     DeviceGuard g(e->device);
     const BatchScope batch_scope(e);  // (an early return clears the pending flag)
     KBatch k = make_kbatch(e, b, iv_state, pos_state);
-#ifdef FPNN_AES_BOUNDS
     if ((rc = audit_begin(e, b, iv_state, pos_state, k))) return rc;
-#endif
     const Layout layout = is_uniform_layout(b) ? LAYOUT_UNIFORM : LAYOUT_GENERAL;
     const KeyMode km = (b->key_slot && b->keys->count > 1) ? KEY_LANE : KEY_UNIFORM;
     // Few chains (fewer than the lanes of a full chip) or ragged lengths: one quad per
@@ -290,34 +316,26 @@ int run_encrypt_calls(fpnn_aes_engine *e, const fpnn_aes_batch *b, uint8_t *iv_s
     const bool k2_ragged = b->len && !stream && b->max_len && b->max_len <= 2048 && b->count >= full_chip;
     if ((b->count < full_chip || b->len != nullptr) && !k2_ragged) {
         const uint64_t lanes = 4 * b->count;
-        int threads = 64;
-        while (threads < kThreads && (uint64_t)threads * e->num_cus < lanes) threads *= 2;
-        const uint64_t want = (lanes + threads - 1) / threads;
-        const int grid = (int)(want < (uint64_t)e->num_cus ? (want ? want : 1) : (uint64_t)e->num_cus);
+        const Spread sp = spread_over_cus(e, lanes);
         // ragged with more chains than quads: K2h (short chains one per lane, the longest
         // on quads, both from work queues); with fewer every quad holds at most one chain
         // and K2c's grid stride is cheaper
         const bool hybrid = b->len && b->count > 1 && (lanes > full_chip || e->variant.hyb_force);
         uint32_t *block = nullptr;  // the length-order block (ragged batches)
-        // (everything that can fail is done before the length order is queued: its block is
-        // left dirty until its last reader runs)
-        if (hybrid && (rc = grow(e, e->d_sink, e->cap_sink, 2ull * e->num_cus * (kThreads / 64)))) return rc;
         if (b->len && b->count > 1) {  // ragged: visit the longest chains first, similar lengths per wave
-            if ((rc = grow(e, e->d_perm, e->cap_perm, b->count))) return rc;
-            if (kLengthOrderWords > e->cap_buckets) {  // starts zeroed; afterwards its last reader zeroes it
-                if ((rc = grow(e, e->d_buckets, e->cap_buckets, kLengthOrderWords))) return rc;
-                HIP_TRY(hipMemsetAsync(e->d_buckets, 0, e->cap_buckets * sizeof(uint32_t), e->stream));
-            }
+            // (everything that can fail is done before the length order is queued: its block is
+            // left dirty until its last reader runs)
+            if ((rc = scratch_ensure(e, need_encrypt_ragged(scratch_shape(e), b->count, hybrid)))) return rc;
             if (stream) {  // bucket sizes read pos_state (the encrypt kernel reads it later)
                 k.pos_snap = pos_state;
             }
-            block = e->d_buckets;
+            block = e->buckets.p;
             if (e->variant.poison_order > 0) {  // (tests) bucket counts left over as if by a lost call
                 e->variant.poison_order--;
                 HIP_TRY(hipMemsetAsync(block, 0x01, kWireFlagWord / 2 * sizeof(uint32_t), e->stream));
             }
-            HIP_TRY(launch_length_order(k, stream, e->d_perm, block, !hybrid, e->d_fault, e->stream));
-            k.perm = e->d_perm;
+            HIP_TRY(launch_length_order(k, stream, e->perm.p, block, !hybrid, e->d_fault, e->stream));
+            k.perm = e->perm.p;
         }
         EventPair *ev;
         if ((rc = timing_begin(e, FPNN_AES_K_ENCRYPT, &ev))) {
@@ -331,7 +349,7 @@ int run_encrypt_calls(fpnn_aes_engine *e, const fpnn_aes_batch *b, uint8_t *iv_s
             h.buckets = block;
             h.long_bucket = length_bucket_of((uint64_t)e->variant.hyb_long);
             h.quad_waves = (uint32_t)e->variant.hyb_quad_waves;
-            h.sink = e->d_sink;
+            h.sink = e->sink.p;
             if (b->flags & FPNN_AES_F_WIRE_PREFIX) {
                 // wire frames (htole32(len) || C): every chain on quads (k_hybrid.hip's
                 // launcher takes the quads-only kernel for them)
@@ -340,7 +358,7 @@ int run_encrypt_calls(fpnn_aes_engine *e, const fpnn_aes_batch *b, uint8_t *iv_s
             }
             HIP_TRY(launch_encrypt_hybrid(k, h, b->keys->nrounds, km, stream, e->num_cus, e->stream));
         } else {
-            HIP_TRY(launch_encrypt_coop(k, b->keys->nrounds, layout, km, stream, grid, threads, e->stream));
+            HIP_TRY(launch_encrypt_coop(k, b->keys->nrounds, layout, km, stream, sp.grid, sp.threads, e->stream));
         }
         return timing_end(e, ev, FPNN_AES_K_ENCRYPT);
     }
@@ -348,11 +366,7 @@ int run_encrypt_calls(fpnn_aes_engine *e, const fpnn_aes_batch *b, uint8_t *iv_s
     // still spreads the chains over every CU -- with few chains (C3: 4096 streams) a
     // 1024-thread workgroup would pack them onto a handful of CUs whose LDS they then
     // saturate, while the rest of the chip idles.
-    const uint64_t slots = (uint64_t)e->num_cus;
-    int threads = 64;
-    while (threads < kThreads && (uint64_t)threads * slots < b->count) threads *= 2;
-    const uint64_t want = (b->count + threads - 1) / threads;
-    const int grid = (int)(want < slots ? (want ? want : 1) : slots);
+    const Spread sp = spread_over_cus(e, b->count);
     // (not for ragged batches by default, Variant::k2_align_ragged: a few 16-B aligned
     // frames per wave made the whole wave run their singles)
     if (!b->len) k.flags |= F_ALIGN_CHUNKS;
@@ -362,8 +376,56 @@ int run_encrypt_calls(fpnn_aes_engine *e, const fpnn_aes_batch *b, uint8_t *iv_s
         HIP_TRY(launch_encrypt_frames(k, b->keys->nrounds, km, (b->flags & FPNN_AES_F_WIRE_PREFIX) != 0,
                                       e->num_cus, e->stream));
     else
-        HIP_TRY(launch_encrypt_chains(k, b->keys->nrounds, layout, km, stream, grid, threads, e->stream));
+        HIP_TRY(launch_encrypt_chains(k, b->keys->nrounds, layout, km, stream, sp.grid, sp.threads, e->stream));
     return timing_end(e, ev, FPNN_AES_K_ENCRYPT);
+}
+
+int run_encrypt(fpnn_aes_engine *e, const fpnn_aes_batch *b, uint8_t *iv_state, uint32_t *pos_state, bool stream) {
+    return audit_end(e, run_encrypt_calls(e, b, iv_state, pos_state, stream));
+}
+
+struct SnapCopy {  // what the single-workgroup block map's state copy reads and writes (stream batches)
+    const uint8_t *iv_from = nullptr;
+    const uint32_t *pos_from = nullptr;
+    uint4 *iv_to = nullptr;
+    uint32_t *pos_to = nullptr;
+};
+
+// K1r on the batch k describes: block-map scan, per-wave plan and decrypt all on the device;
+// the host never learns the block total, so nothing here waits for the GPU.  What can fail
+// comes first: the scratch (`need`) is grown before anything is queued.  before(small_map,
+// snap) then queues what the caller runs ahead of the block map (state snapshot or pre-pass),
+// points k at it and says what a small (single-workgroup) block map copies as its snapshot.
+template <class Before>
+int decrypt_ragged(fpnn_aes_engine *e, const fpnn_aes_batch *b, KBatch &k, bool stream, KeyMode km,
+                   const ScratchNeed &need, Before before) {
+    if (int rc = scratch_ensure(e, need)) return rc;
+    const bool small_map = b->count <= block_map_small_max();
+    SnapCopy snap;
+    if (int rc = before(small_map, snap)) return rc;
+    if (small_map)
+        HIP_TRY(launch_block_map_small(k, stream, snap.iv_from, snap.pos_from, snap.iv_to, snap.pos_to, e->bstart.p,
+                                       e->d_total, e->stream));
+    else  // (its look-back words: zeros when grown, zeroed again by the kernel's last reader)
+        HIP_TRY(launch_block_map_onepass(k, stream, e->bstart.p, e->lookback.p, e->lookback.cap, e->d_fault,
+                                         e->d_total, e->stream));
+    k.bstart = e->bstart.p;
+    if (!k.in_off || !k.len) {  // K1r reads descriptor arrays: materialize the missing ones
+        HIP_TRY(launch_ragged_desc(b->count, b->stride, b->uniform_len, k.in_off ? nullptr : e->desc_off.p,
+                                   k.len ? nullptr : e->desc_len.p, e->stream));
+        if (!k.in_off) k.in_off = e->desc_off.p;
+        if (!k.len) k.len = e->desc_len.p;
+    }
+    if (!k.out_off) k.out_off = k.in_off;
+    k.runs = (uint32_t)e->variant.k1r_runs;
+    EventPair *ev = nullptr;
+    if (int rc = timing_begin(e, FPNN_AES_K_DECRYPT, &ev)) return rc;
+    // in place (in == out, identical offsets: fpnn_aes.h) the predecessor blocks of the
+    // waves' first chunks are saved by a plan launch before any wave writes; otherwise
+    // every wave finds its own at the start of the decrypt kernel (one launch fewer)
+    HIP_TRY(launch_decrypt_ragged(k, b->keys->nrounds, km, stream, e->plan.p, e->sink.p, b->in == b->out, e->num_cus,
+                                  e->stream));
+    return timing_end(e, ev, FPNN_AES_K_DECRYPT);
 }
 
 int run_decrypt(fpnn_aes_engine *e, const fpnn_aes_batch *b, uint8_t *iv_state, uint32_t *pos_state, bool stream) {
@@ -375,18 +437,6 @@ int run_decrypt(fpnn_aes_engine *e, const fpnn_aes_batch *b, uint8_t *iv_state, 
     DeviceGuard g(e->device);
     const BatchScope batch_scope(e);  // (an early return clears the pending flag)
     KBatch k = make_kbatch(e, b, iv_state, pos_state);
-    // small ragged batches: block map (+ stream snapshot) in one single-workgroup kernel
-    const bool small_map = b->count <= block_map_small_max();
-    if (stream) {  // snapshot the incoming (iv, pos) state, see KBatch::iv_snap
-        if ((rc = grow(e, e->d_snap_iv, e->cap_snap_iv, b->count))) return rc;
-        if ((rc = grow(e, e->d_snap_pos, e->cap_snap_pos, b->count))) return rc;
-        if (!small_map) {  // (stream batches always take the general layout below)
-            HIP_TRY(hipMemcpyAsync(e->d_snap_iv, iv_state, 16ull * b->count, hipMemcpyDeviceToDevice, e->stream));
-            HIP_TRY(hipMemcpyAsync(e->d_snap_pos, pos_state, 4ull * b->count, hipMemcpyDeviceToDevice, e->stream));
-        }
-        k.iv_snap = e->d_snap_iv;
-        k.pos_snap = e->d_snap_pos;
-    }
     // In place whenever the buffers coincide (K1 / K1d: a wave may overwrite the
     // ciphertext block another wave's lane 0 still needs, so chunk boundaries are saved
     // first; K1r saves its waves' boundaries in its plan in any case).
@@ -396,28 +446,23 @@ int run_decrypt(fpnn_aes_engine *e, const fpnn_aes_batch *b, uint8_t *iv_state, 
     // (Stream mode only when there is a single segment, whose position the caller
     // supplies through the host path; otherwise positions differ per stream.)
     Layout layout = LAYOUT_GENERAL;
+    auto uniform_blocks = [&](uint64_t nb, Layout l) {  // nb blocks per segment, fewer than 2^32 in all
+        layout = l;
+        k.total_blocks = nb * b->count;
+        k.nb_uniform = (uint32_t)nb;
+        k.magic = magic_for((uint32_t)nb);
+    };
     if (is_uniform_layout(b) && !stream) {
         const uint64_t nb = ((uint64_t)b->uniform_len + 15) >> 4;
-        const uint64_t total = nb * b->count;
-        if (nb > 0 && total < (1ull << 32) && nb > 1) {
-            layout = (b->uniform_len & 15) == 0 ? LAYOUT_FULL : LAYOUT_UNIFORM;
-            k.total_blocks = total;
-            k.nb_uniform = (uint32_t)nb;
-            k.magic = magic_for((uint32_t)nb);
-        }
+        if (nb > 1 && nb * b->count < (1ull << 32))
+            uniform_blocks(nb, (b->uniform_len & 15) == 0 ? LAYOUT_FULL : LAYOUT_UNIFORM);
     } else if (!stream && km == KEY_LANE && !b->in_off && !b->out_off && !b->len &&
                b->uniform_len >= 32 && b->uniform_len % 16 == 0 && b->stride == b->uniform_len) {
         // dense whole-block packets, one key slot each: K1d with a wave-uniform key per
         // step when packets are whole 64-block chunks (C5), K1k with per-lane keys
         // otherwise (U1)
         const uint64_t nb = b->uniform_len >> 4;
-        const uint64_t total = nb * b->count;
-        if (total < (1ull << 32)) {
-            layout = LAYOUT_FULL;
-            k.total_blocks = total;
-            k.nb_uniform = (uint32_t)nb;
-            k.magic = magic_for((uint32_t)nb);
-        }
+        if (nb * b->count < (1ull << 32)) uniform_blocks(nb, LAYOUT_FULL);
     }
     // Ragged package batches of FPNN's quests (the caller's max_len bound, at least one frame
     // per GPU lane): one lane per frame, its blocks decrypted as independent AES passes from
@@ -429,51 +474,29 @@ int run_decrypt(fpnn_aes_engine *e, const fpnn_aes_batch *b, uint8_t *iv_state, 
         HIP_TRY(launch_decrypt_frames(k, b->keys->nrounds, km, e->num_cus, e->stream));
         return timing_end(e, ev, FPNN_AES_K_DECRYPT);
     }
-    if (layout == LAYOUT_GENERAL) {
-        // K1r: block-map scan, per-wave plan and decrypt all on the device; the host
-        // never learns the block total, so nothing here waits for the GPU
-        if ((rc = grow(e, e->d_bstart, e->cap_bstart, b->count + 1))) return rc;
-        const int grid = e->num_cus;
-        if ((rc = grow(e, e->d_plan, e->cap_plan, (uint64_t)grid * (kThreads / 64)))) return rc;
-        if ((rc = grow(e, e->d_sink, e->cap_sink, 2ull * grid * (kThreads / 64)))) return rc;
-        if (small_map)
-            HIP_TRY(launch_block_map_small(k, stream, iv_state, pos_state, e->d_snap_iv, e->d_snap_pos, e->d_bstart,
-                                           e->d_total, e->stream));
-        else {
-            const uint64_t words = block_map_onepass_words(b->count);
-            if (words > e->cap_lookback) {  // the kernel expects zeros on first use
-                if ((rc = grow(e, e->d_lookback, e->cap_lookback, words))) return rc;
-                HIP_TRY(hipMemsetAsync(e->d_lookback, 0, e->cap_lookback * sizeof(uint64_t), e->stream));
-            }
-            HIP_TRY(launch_block_map_onepass(k, stream, e->d_bstart, e->d_lookback, e->cap_lookback, e->d_fault,
-                                             e->d_total, e->stream));
-        }
-        k.bstart = e->d_bstart;
-        if (!k.in_off || !k.len) {  // K1r reads descriptor arrays: materialize the missing ones
-            if (!k.in_off && (rc = grow(e, e->d_desc_off, e->cap_desc_off, b->count))) return rc;
-            if (!k.len && (rc = grow(e, e->d_desc_len, e->cap_desc_len, b->count))) return rc;
-            HIP_TRY(launch_ragged_desc(b->count, b->stride, b->uniform_len, k.in_off ? nullptr : e->d_desc_off,
-                                       k.len ? nullptr : e->d_desc_len, e->stream));
-            if (!k.in_off) k.in_off = e->d_desc_off;
-            if (!k.len) k.len = e->d_desc_len;
-        }
-        if (!k.out_off) k.out_off = k.in_off;
-        k.runs = (uint32_t)e->variant.k1r_runs;
-        EventPair *ev = nullptr;
-        if ((rc = timing_begin(e, FPNN_AES_K_DECRYPT, &ev))) return rc;
-        // in place (in == out, identical offsets: fpnn_aes.h) the predecessor blocks of the
-        // waves' first chunks are saved by a plan launch before any wave writes; otherwise
-        // every wave finds its own at the start of the decrypt kernel (one launch fewer)
-        HIP_TRY(launch_decrypt_ragged(k, b->keys->nrounds, km, stream, e->d_plan, e->d_sink, inplace, grid,
-                                      e->stream));
-        return timing_end(e, ev, FPNN_AES_K_DECRYPT);
+    if (layout == LAYOUT_GENERAL) {  // K1r; stream batches (which always come here) snapshot their state first
+        const uint64_t n = b->count;
+        return decrypt_ragged(e, b, k, stream, km, need_decrypt_ragged(scratch_shape(e), n, stream, b->in_off, b->len),
+                              [&](bool small_map, SnapCopy &snap) {
+                                  if (!stream) return (int)FPNN_AES_OK;
+                                  if (!small_map) {  // (the small block map copies the snapshot itself)
+                                      HIP_TRY(hipMemcpyAsync(e->snap_iv.p, iv_state, 16ull * n, hipMemcpyDeviceToDevice,
+                                                             e->stream));
+                                      HIP_TRY(hipMemcpyAsync(e->snap_pos.p, pos_state, 4ull * n, hipMemcpyDeviceToDevice,
+                                                             e->stream));
+                                  }
+                                  k.iv_snap = e->snap_iv.p;  // see KBatch::iv_snap
+                                  k.pos_snap = e->snap_pos.p;
+                                  snap = {iv_state, pos_state, e->snap_iv.p, e->snap_pos.p};
+                                  return (int)FPNN_AES_OK;
+                              });
     }
     EventPair *ev = nullptr;
     const uint64_t nchunks = (k.total_blocks + 63) >> 6;
     if (inplace) {
-        if ((rc = grow(e, e->d_boundary, e->cap_boundary, nchunks))) return rc;
-        HIP_TRY(launch_boundary_save(k, e->d_boundary, nchunks, e->stream));
-        k.boundary = e->d_boundary;
+        if ((rc = scratch_ensure(e, need_decrypt_dense_inplace(k.total_blocks)))) return rc;
+        HIP_TRY(launch_boundary_save(k, e->boundary.p, nchunks, e->stream));
+        k.boundary = e->boundary.p;
     }
     const uint64_t want = (nchunks + 63) / 64;  // 16 waves per workgroup x up to 4 chunks per wave step
     const uint64_t cap = (uint64_t)e->num_cus;
@@ -531,19 +554,13 @@ int run_encrypt_frames_calls(fpnn_aes_engine *e, const fpnn_aes_batch *b, const 
     const BatchScope batch_scope(e);  // (an early return clears the pending flag)
     KBatch k = make_kbatch(e, b, iv_state, pos_state);
     const FrameTable f = frame_table(e, first_frame, nstreams, at);
-#ifdef FPNN_AES_BOUNDS
     if ((rc = audit_begin(e, b, iv_state, pos_state, k, &f))) return rc;
-#endif
     // (an _at call: every stream's key from its slot of the table, whatever the table's size)
     const KeyMode km = (at || (b->key_slot && b->keys->count > 1)) ? KEY_LANE : KEY_UNIFORM;
-    const uint64_t lanes = 4ull * nstreams;
-    int threads = 64;
-    while (threads < kThreads && (uint64_t)threads * e->num_cus < lanes) threads *= 2;
-    const uint64_t want = (lanes + threads - 1) / threads;
-    const int grid = (int)(want < (uint64_t)e->num_cus ? want : (uint64_t)e->num_cus);
+    const Spread sp = spread_over_cus(e, 4ull * nstreams);
     EventPair *ev;
     if ((rc = timing_begin(e, FPNN_AES_K_ENCRYPT, &ev))) return rc;
-    HIP_TRY(launch_encrypt_stream_frames(k, f, b->keys->nrounds, km, grid, threads, e->stream));
+    HIP_TRY(launch_encrypt_stream_frames(k, f, b->keys->nrounds, km, sp.grid, sp.threads, e->stream));
     return timing_end(e, ev, FPNN_AES_K_ENCRYPT);
 }
 
@@ -558,84 +575,44 @@ int run_decrypt_frames_calls(fpnn_aes_engine *e, const fpnn_aes_batch *b, const 
     if (!nstreams || !b->count) return FPNN_AES_OK;
     DeviceGuard g(e->device);
     const BatchScope batch_scope(e);
-    const uint64_t n = b->count;
-    const int grid = e->num_cus;
-    // (everything that can fail first: nothing is queued before the scratch stands)
-    if ((rc = grow(e, e->d_snap_iv, e->cap_snap_iv, n))) return rc;
-    if ((rc = grow(e, e->d_snap_pos, e->cap_snap_pos, n))) return rc;
-    if ((rc = grow(e, e->d_sf_stream, e->cap_sf_stream, n))) return rc;
-    if ((rc = grow(e, e->d_sf_prev, e->cap_sf_prev, n))) return rc;
-    if ((rc = grow(e, e->d_sf_iv, e->cap_sf_iv, n))) return rc;
-    if ((rc = grow(e, e->d_sf_pos, e->cap_sf_pos, n))) return rc;
-    if (at && (rc = grow(e, e->d_sf_slot, e->cap_sf_slot, n))) return rc;
-    if ((rc = grow(e, e->d_bstart, e->cap_bstart, n + 1))) return rc;
-    if ((rc = grow(e, e->d_plan, e->cap_plan, (uint64_t)grid * (kThreads / 64)))) return rc;
-    if ((rc = grow(e, e->d_sink, e->cap_sink, 2ull * grid * (kThreads / 64)))) return rc;
-    if (!b->in_off && (rc = grow(e, e->d_desc_off, e->cap_desc_off, n))) return rc;
-    if (!b->len && (rc = grow(e, e->d_desc_len, e->cap_desc_len, n))) return rc;
-    const bool small_map = n <= block_map_small_max();
-    if (!small_map && block_map_onepass_words(n) > e->cap_lookback) {  // the kernel expects zeros on first use
-        if ((rc = grow(e, e->d_lookback, e->cap_lookback, block_map_onepass_words(n)))) return rc;
-        HIP_TRY(hipMemsetAsync(e->d_lookback, 0, e->cap_lookback * sizeof(uint64_t), e->stream));
-    }
     KBatch k = make_kbatch(e, b, iv_state, pos_state);
     FrameTable f = frame_table(e, first_frame, nstreams, at);
-    if (at) {  // the walk writes every segment's key slot; the pre-pass's second launch and K1r read it
-        f.seg_slot = e->d_sf_slot;
-        k.key_slot = e->d_sf_slot;
-    }
-#ifdef FPNN_AES_BOUNDS
-    if ((rc = audit_begin(e, b, iv_state, pos_state, k, &f))) return rc;
-#endif
     const KeyMode km = (at || (b->key_slot && b->keys->count > 1)) ? KEY_LANE : KEY_UNIFORM;
-    // the pre-pass reads the ciphertext and the incoming state: before the block map (whose
-    // block counts read pos_snap) and before any in-place write
-    HIP_TRY(launch_stream_frames_state(k, f, b->keys->nrounds, km, e->d_snap_iv, e->d_snap_pos, e->d_sf_stream,
-                                       e->d_sf_prev, e->num_cus, e->stream));
-    k.iv_snap = e->d_snap_iv;
-    k.pos_snap = e->d_snap_pos;
-    // from here on "the state" is per segment: K1r exports into the scratch
-    k.iv_state = reinterpret_cast<uint8_t *>(e->d_sf_iv);
-    k.pos_state = e->d_sf_pos;
-    if (small_map)
-        // (its snapshot copy goes from the pre-pass's snapshot into the export scratch, which
-        // K1r overwrites: the snapshot itself stays as the pre-pass wrote it)
-        HIP_TRY(launch_block_map_small(k, true, reinterpret_cast<const uint8_t *>(e->d_snap_iv), e->d_snap_pos, e->d_sf_iv,
-                                       e->d_sf_pos, e->d_bstart, e->d_total, e->stream));
-    else
-        HIP_TRY(launch_block_map_onepass(k, true, e->d_bstart, e->d_lookback, e->cap_lookback, e->d_fault, e->d_total,
-                                         e->stream));
-    k.bstart = e->d_bstart;
-    if (!k.in_off || !k.len) {  // K1r reads descriptor arrays: materialize the missing ones
-        HIP_TRY(launch_ragged_desc(n, b->stride, b->uniform_len, k.in_off ? nullptr : e->d_desc_off,
-                                   k.len ? nullptr : e->d_desc_len, e->stream));
-        if (!k.in_off) k.in_off = e->d_desc_off;
-        if (!k.len) k.len = e->d_desc_len;
-    }
-    if (!k.out_off) k.out_off = k.in_off;
-    k.runs = (uint32_t)e->variant.k1r_runs;
-    EventPair *ev = nullptr;
-    if ((rc = timing_begin(e, FPNN_AES_K_DECRYPT, &ev))) return rc;
-    HIP_TRY(launch_decrypt_ragged(k, b->keys->nrounds, km, true, e->d_plan, e->d_sink, b->in == b->out, grid,
-                                  e->stream));
-    if ((rc = timing_end(e, ev, FPNN_AES_K_DECRYPT))) return rc;
+    rc = decrypt_ragged(
+        e, b, k, true, km, need_decrypt_frames(scratch_shape(e), b->count, at != nullptr, b->in_off, b->len),
+        [&](bool, SnapCopy &snap) {
+            if (at) {  // the walk writes every segment's key slot; the pre-pass's second launch and K1r read it
+                f.seg_slot = e->sf_slot.p;
+                k.key_slot = e->sf_slot.p;
+            }
+            if (int arc = audit_begin(e, b, iv_state, pos_state, k, &f)) return arc;
+            // the pre-pass reads the ciphertext and the incoming state: before the block map (whose
+            // block counts read pos_snap) and before any in-place write
+            HIP_TRY(launch_stream_frames_state(k, f, b->keys->nrounds, km, e->snap_iv.p, e->snap_pos.p, e->sf_stream.p,
+                                               e->sf_prev.p, e->num_cus, e->stream));
+            k.iv_snap = e->snap_iv.p;
+            k.pos_snap = e->snap_pos.p;
+            // from here on "the state" is per segment: K1r exports into the scratch
+            k.iv_state = reinterpret_cast<uint8_t *>(e->sf_iv.p);
+            k.pos_state = e->sf_pos.p;
+            // (a small block map's snapshot copy goes from the pre-pass's snapshot into the export
+            // scratch, which K1r overwrites: the snapshot itself stays as the pre-pass wrote it)
+            snap = {reinterpret_cast<const uint8_t *>(e->snap_iv.p), e->snap_pos.p, e->sf_iv.p, e->sf_pos.p};
+            return (int)FPNN_AES_OK;
+        });
+    if (rc) return rc;
     k.iv_state = iv_state;
     k.pos_state = pos_state;
     k.len = b->len;  // (as the caller gave it: uniform_len otherwise)
-    HIP_TRY(launch_stream_frames_commit(k, f, e->d_sf_iv, e->d_sf_pos, e->stream));
+    HIP_TRY(launch_stream_frames_commit(k, f, e->sf_iv.p, e->sf_pos.p, e->stream));
     batch_queued(e);  // (the call's batch work ends behind the commit)
     return FPNN_AES_OK;
 }
 
 int run_frames(fpnn_aes_engine *e, const fpnn_aes_batch *b, const uint32_t *first_frame, uint32_t nstreams,
                uint8_t *iv_state, uint32_t *pos_state, bool encrypt, const SlotAddr *at = nullptr) {
-    const int rc = encrypt ? run_encrypt_frames_calls(e, b, first_frame, nstreams, iv_state, pos_state, at)
-                           : run_decrypt_frames_calls(e, b, first_frame, nstreams, iv_state, pos_state, at);
-#ifdef FPNN_AES_BOUNDS
-    return audit_end(e, rc);
-#else
-    return rc;
-#endif
+    return audit_end(e, encrypt ? run_encrypt_frames_calls(e, b, first_frame, nstreams, iv_state, pos_state, at)
+                                : run_decrypt_frames_calls(e, b, first_frame, nstreams, iv_state, pos_state, at));
 }
 
 }  // namespace
@@ -782,13 +759,9 @@ int fpnn_aes_engine_destroy(fpnn_aes_engine *e) {
     DeviceGuard g(e->device);
     if (e->stream) (void)hipStreamSynchronize(e->stream);
     (void)hipFree(e->d_tables);
-    for (void *p : {(void *)e->d_bstart, (void *)e->d_boundary, (void *)e->d_snap_iv,
-                    (void *)e->d_snap_pos, (void *)e->d_perm, (void *)e->d_buckets,
-                    (void *)e->d_fr_off, (void *)e->d_fr_slot, (void *)e->d_plan, (void *)e->d_sink,
-                    (void *)e->d_desc_off, (void *)e->d_desc_len, (void *)e->d_ecdh, (void *)e->d_sstate,
-                    (void *)e->d_lookback, (void *)e->d_sf_stream, (void *)e->d_sf_prev, (void *)e->d_sf_iv,
-                    (void *)e->d_sf_pos, (void *)e->d_sf_slot})
-        release_scratch(e, p);
+#define X(name, type, zeroed) if (e->name.p) (void)(e->pools ? hipFreeAsync(e->name.p, e->stream) : hipFree(e->name.p));
+    FPNN_AES_SCRATCH_BUFFERS(X)  // (every scratch buffer; the stream is idle)
+#undef X
     if (e->stream) (void)hipStreamSynchronize(e->stream);
     free_deferred(e);
     if (e->mpool) {  // (its blocks were freed above, behind the stream)
@@ -883,36 +856,8 @@ int fpnn_aes_max_thread_engines(int ndev) {
 int fpnn_aes_engine_reserve(fpnn_aes_engine *e, uint64_t max_segments, uint64_t max_blocks) {
     if (!e) return FPNN_AES_ERR_ARG;
     DeviceGuard g(e->device);
-    int rc;
-    if ((rc = grow(e, e->d_bstart, e->cap_bstart, max_segments + 1))) return rc;
-    if (block_map_onepass_words(max_segments) > e->cap_lookback) {
-        if ((rc = grow(e, e->d_lookback, e->cap_lookback, block_map_onepass_words(max_segments)))) return rc;
-        HIP_TRY(hipMemsetAsync(e->d_lookback, 0, e->cap_lookback * sizeof(uint64_t), e->stream));
-    }
-    const uint64_t nchunks = (max_blocks + 63) / 64;
-    if ((rc = grow(e, e->d_boundary, e->cap_boundary, nchunks + 1))) return rc;
-    const uint64_t nwaves = (uint64_t)e->num_cus * (kThreads / 64);
-    if ((rc = grow(e, e->d_plan, e->cap_plan, nwaves))) return rc;
-    if ((rc = grow(e, e->d_sink, e->cap_sink, 2 * nwaves))) return rc;
-    // ragged encrypt ordering, stream-decrypt snapshot, materialised descriptors
-    if ((rc = grow(e, e->d_perm, e->cap_perm, max_segments))) return rc;
-    if (kLengthOrderWords > e->cap_buckets) {
-        if ((rc = grow(e, e->d_buckets, e->cap_buckets, kLengthOrderWords))) return rc;
-        HIP_TRY(hipMemsetAsync(e->d_buckets, 0, e->cap_buckets * sizeof(uint32_t), e->stream));
-    }
-    if ((rc = grow(e, e->d_snap_iv, e->cap_snap_iv, max_segments))) return rc;
-    if ((rc = grow(e, e->d_snap_pos, e->cap_snap_pos, max_segments))) return rc;
-    if ((rc = grow(e, e->d_desc_off, e->cap_desc_off, max_segments))) return rc;
-    if ((rc = grow(e, e->d_desc_len, e->cap_desc_len, max_segments))) return rc;
-    // the *_frames decrypt pre-pass and K1r's per-segment state
-    if ((rc = grow(e, e->d_sf_stream, e->cap_sf_stream, max_segments))) return rc;
-    if ((rc = grow(e, e->d_sf_prev, e->cap_sf_prev, max_segments))) return rc;
-    if ((rc = grow(e, e->d_sf_iv, e->cap_sf_iv, max_segments))) return rc;
-    if ((rc = grow(e, e->d_sf_pos, e->cap_sf_pos, max_segments))) return rc;
-    if ((rc = grow(e, e->d_sf_slot, e->cap_sf_slot, max_segments))) return rc;
-    // fpnn_ecdh_accept of up to max_segments peers: key (<= 32) | iv (16) | ok (1) each
-    if ((rc = grow(e, e->d_ecdh, e->cap_ecdh, max_segments * (32 + 16 + 1)))) return rc;
-    return FPNN_AES_OK;
+    // every call path at these bounds: calls within them then neither allocate nor memset
+    return scratch_ensure(e, need_reserve(scratch_shape(e), max_segments, max_blocks));
 }
 
 // ---- key sets ---------------------------------------------------------------
@@ -975,12 +920,7 @@ int fpnn_aes_keyset_from_schedules(fpnn_aes_engine *e, uint32_t count, const fpn
     std::vector<DevKey> host(count);
     for (uint32_t i = 0; i < count; i++) {
         if (ctx[i].nrounds != nr) return FPNN_AES_ERR_ARG;
-        DevKey &d = host[i];
-        memset(&d, 0, sizeof d);
-        for (int k = 0; k < 4 * (nr + 1); k++) d.rk[k] = bswap32(ctx[i].rk[k]);
-        d.nrounds = (uint32_t)nr;
-        d.keylen = (uint32_t)(nr - 6) * 4;
-        if (ivs) memcpy(d.iv, ivs + 16 * (size_t)i, 16);
+        devkey_from_schedule(&host[i], &ctx[i], ivs ? ivs + 16 * (size_t)i : nullptr);
     }
     DeviceGuard g(e->device);
     fpnn_aes_keyset *ks = new fpnn_aes_keyset();
@@ -1111,14 +1051,8 @@ int fpnn_aes_keyset_set(fpnn_aes_keyset *ks, uint32_t first, uint32_t count, con
         HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&ks->h_up), sizeof(DevKey) * (size_t)c, 0));
         ks->cap_up = c;
     }
-    for (uint32_t i = 0; i < count; i++) {
-        DevKey &d = ks->h_up[i];
-        memset(&d, 0, sizeof d);
-        for (int k = 0; k < 4 * (ks->nrounds + 1); k++) d.rk[k] = bswap32(ctx[i].rk[k]);
-        d.nrounds = (uint32_t)ks->nrounds;
-        d.keylen = ks->keylen;
-        if (ivs) memcpy(d.iv, ivs + 16 * (size_t)i, 16);
-    }
+    for (uint32_t i = 0; i < count; i++)  // (every ctx[i].nrounds is the table's, checked above)
+        devkey_from_schedule(&ks->h_up[i], &ctx[i], ivs ? ivs + 16 * (size_t)i : nullptr);
     HIP_TRY(hipMemcpyAsync(ks->d_keys + first, ks->h_up, sizeof(DevKey) * (size_t)count, hipMemcpyHostToDevice,
                            e->stream));
     HIP_TRY(hipEventRecord(ks->up_done, e->stream));
@@ -1173,33 +1107,11 @@ static int keytable_run(fpnn_aes_keyset *ks, KeyTableArgs &a, bool set) {
     fpnn_aes_engine *e = ks->e;
     DeviceGuard g(ks->device);
     const BatchScope batch_scope(e);  // (an early return clears the pending flag)
-#ifdef FPNN_AES_BOUNDS
-    if (!e->d_aud) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->d_aud), sizeof(AuditTable)));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    AuditTable t;
-    memset(&t, 0, sizeof t);
-    auto ext = [&](AuditBuf i, const void *p, uint64_t bytes) {
-        if (!p) return;
-        t.lo[i] = (uint64_t)(uintptr_t)p;
-        t.hi[i] = t.lo[i] + bytes;
-    };
-    ext(AB_KEYS, a.keys, sizeof(DevKey) * (uint64_t)table_slots(ks));
-    ext(AB_EIV, a.eiv, 16 * (uint64_t)table_slots(ks));
-    ext(AB_KT_SLOTS, a.slots, 4 * (uint64_t)a.count);
-    ext(AB_KT_RAW, a.raw, (uint64_t)ks->keylen * a.count);
-    ext(AB_KT_IVS, a.ivs, 16 * (uint64_t)a.count);
-    ext(AB_KT_OK, a.ok, a.count);
-    HIP_TRY(hipMemcpy(e->d_aud, &t, sizeof t, hipMemcpyHostToDevice));
-    a.aud = e->d_aud;
-#endif
+    if (int rc = audit_begin_keytable(e, ks, a)) return rc;
     HIP_TRY(set ? launch_set_keys(a, ks->keylen, e->stream) : launch_clear_slots(a, ks->nrounds, e->stream));
     batch_queued(e);
     ks->count = std::max(ks->count, a.slot_bound);
-#ifdef FPNN_AES_BOUNDS
     return audit_end(e, FPNN_AES_OK);
-#else
-    return FPNN_AES_OK;
-#endif
 }
 
 int fpnn_aes_keyset_set_keys(fpnn_aes_keyset *ks, uint32_t first, uint32_t count, const uint32_t *slots,
@@ -1251,31 +1163,10 @@ static int stream_state_run(fpnn_aes_keyset *ks, uint32_t first, uint32_t count,
     a.pos_state = pos_state;
     a.fault = e->d_fault;
     const BatchScope batch_scope(e);  // (an early return clears the pending flag)
-#ifdef FPNN_AES_BOUNDS
-    if (!e->d_aud) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->d_aud), sizeof(AuditTable)));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    AuditTable t;
-    memset(&t, 0, sizeof t);
-    auto ext = [&](AuditBuf i, const void *p, uint64_t bytes) {
-        if (!p) return;
-        t.lo[i] = (uint64_t)(uintptr_t)p;
-        t.hi[i] = t.lo[i] + bytes;
-    };
-    ext(AB_KEYS, a.keys, sizeof(DevKey) * (uint64_t)table_slots(ks));
-    ext(AB_KT_SLOTS, a.slots, 4 * (uint64_t)a.count);
-    ext(AB_KT_OK, a.ok, a.count);
-    ext(AB_IV_STATE, a.iv_state, 16 * (uint64_t)bound);
-    ext(AB_POS_STATE, a.pos_state, 4 * (uint64_t)bound);
-    HIP_TRY(hipMemcpy(e->d_aud, &t, sizeof t, hipMemcpyHostToDevice));
-    a.aud = e->d_aud;
-#endif
+    if (int rc = audit_begin_keytable(e, ks, a)) return rc;
     HIP_TRY(open ? launch_stream_open(a, e->stream) : launch_stream_close(a, e->stream));
     batch_queued(e);
-#ifdef FPNN_AES_BOUNDS
     return audit_end(e, FPNN_AES_OK);
-#else
-    return FPNN_AES_OK;
-#endif
 }
 
 int fpnn_aes_stream_open(fpnn_aes_keyset *ks, uint32_t first, uint32_t count, const uint32_t *slots,
@@ -1345,8 +1236,8 @@ int fpnn_aes_package_recv(fpnn_aes_engine *e, const fpnn_aes_batch *b, uint32_t 
     if (slots > 0xffffffffull) return FPNN_AES_ERR_RANGE;
     DeviceGuard g(e->device);
     const bool per_key = b->key_slot && b->keys->count > 1;
-    if ((rc = grow(e, e->d_fr_off, e->cap_fr_off, slots))) return rc;
-    if (per_key && (rc = grow(e, e->d_fr_slot, e->cap_fr_slot, slots))) return rc;
+    if ((rc = e->fr_off.ensure(e, slots))) return rc;
+    if (per_key && (rc = e->fr_slot.ensure(e, slots))) return rc;
     KScan s;
     memset(&s, 0, sizeof s);
     s.buf = b->in;
@@ -1361,8 +1252,8 @@ int fpnn_aes_package_recv(fpnn_aes_engine *e, const fpnn_aes_batch *b, uint32_t 
     s.frame_off = frame_off;
     s.frame_len = frame_len;
     s.scan = reinterpret_cast<ScanResult *>(scan);
-    s.abs_off = e->d_fr_off;
-    s.abs_slot = per_key ? e->d_fr_slot : nullptr;
+    s.abs_off = e->fr_off.p;
+    s.abs_slot = per_key ? e->fr_slot.p : nullptr;
     static_assert(sizeof(ScanResult) == sizeof(fpnn_aes_frame_scan), "scan layout");
     const BatchScope batch_scope(e);  // (an early return clears the pending flag)
     HIP_TRY(launch_scan_frames(s, false, e->num_cus, e->stream));
@@ -1373,9 +1264,9 @@ int fpnn_aes_package_recv(fpnn_aes_engine *e, const fpnn_aes_batch *b, uint32_t 
     fb.in = b->in;
     fb.out = b->out;
     fb.count = (uint32_t)slots;
-    fb.in_off = e->d_fr_off;
+    fb.in_off = e->fr_off.p;
     fb.len = frame_len;
-    fb.key_slot = per_key ? e->d_fr_slot : nullptr;
+    fb.key_slot = per_key ? e->fr_slot.p : nullptr;
     fb.keys = b->keys;
     fb.max_len = max_len;  // (every frame the scan accepts is within it: D2s for FPNN's quests)
     return run_decrypt(e, &fb, nullptr, nullptr, false);
@@ -1450,13 +1341,6 @@ int stage_reserve(fpnn_aes_engine *e, uint64_t need) {
     HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e->d_stage), n));
     e->cap_stage = n;
     return FPNN_AES_OK;
-}
-
-// DevKey of a host schedule (rijndael_context layout, big-endian rk words)
-void devkey_from_schedule(DevKey *hk, const fpnn_aes_schedule *ctx) {
-    memset(hk, 0, sizeof *hk);
-    for (int k = 0; k < 4 * (ctx->nrounds + 1); k++) hk->rk[k] = bswap32(ctx->rk[k]);
-    hk->nrounds = (uint32_t)ctx->nrounds;
 }
 
 bool valid_rounds(int nr) { return nr == 10 || nr == 12 || nr == 14; }
@@ -1952,12 +1836,12 @@ int ecdh_const(int curve, EccConst &c) {
 
 bool aligned4(const void *p) { return ((uintptr_t)p & 3u) == 0; }
 
-// d_ecdh held derived keys (or a private key): zero the bytes the call used, queued behind
+// the ecdh scratch held derived keys (or a private key): zero the bytes the call used, queued behind
 // their last reader on the engine's stream.
 int ecdh_wipe(fpnn_aes_engine *e, size_t bytes) {
-    if (!e->d_ecdh || !bytes) return FPNN_AES_OK;
+    if (!e->ecdh.p || !bytes) return FPNN_AES_OK;
     DeviceGuard g(e->device);
-    HIP_TRY(hipMemsetAsync(e->d_ecdh, 0, std::min<uint64_t>(bytes, e->cap_ecdh), e->stream));
+    HIP_TRY(hipMemsetAsync(e->ecdh.p, 0, std::min<uint64_t>(bytes, e->ecdh.cap), e->stream));
     return FPNN_AES_OK;
 }
 
@@ -2091,9 +1975,9 @@ int fpnn_ecdh_keyset(fpnn_aes_engine *e, int curve, const uint8_t *private_key, 
     if (keylen != 16 && keylen != 32) return FPNN_AES_ERR_KEYLEN;
     DeviceGuard g(e->device);
     const size_t kb = (size_t)count * keylen, ib = (size_t)count * 16;
-    int rc = grow(e, e->d_ecdh, e->cap_ecdh, kb + ib + count);  // keys | ivs | ok, engine scratch
+    int rc = e->ecdh.ensure(e, kb + ib + count);  // keys | ivs | ok, engine scratch
     if (rc) return rc;
-    uint8_t *tmp = e->d_ecdh;
+    uint8_t *tmp = e->ecdh.p;
     rc = fpnn_ecdh_calc_keys(e, curve, private_key, peer_public, count, keylen, tmp, tmp + kb, ok ? ok : tmp + kb + ib);
     if (!rc) rc = fpnn_aes_keyset_create(e, count, (size_t)keylen, tmp, tmp + kb, 0, out);  // synchronizes
     const int wrc = ecdh_wipe(e, kb + ib + count);
@@ -2116,9 +2000,9 @@ int fpnn_ecdh_accept(fpnn_aes_engine *e, int curve, const uint8_t *private_key, 
     DeviceGuard g(e->device);
     const int keylen = (int)ks->keylen;
     const size_t kb = (size_t)count * keylen, ib = (size_t)count * 16;
-    rc = grow(e, e->d_ecdh, e->cap_ecdh, kb + ib + count);  // keys | ivs | ok, engine scratch
+    rc = scratch_ensure(e, need_ecdh_accept(count, (uint64_t)keylen));  // keys | ivs | ok, engine scratch
     if (rc) return rc;
-    uint8_t *tmp = e->d_ecdh, *okp = ok ? ok : tmp + kb + ib;
+    uint8_t *tmp = e->ecdh.p, *okp = ok ? ok : tmp + kb + ib;
     rc = fpnn_ecdh_calc_keys(e, curve, private_key, peer_public, count, keylen, tmp, tmp + kb, okp);
     if (!rc) {
         a.raw = tmp;
@@ -2139,9 +2023,9 @@ int fpnn_ecdh_calc_keys_host(fpnn_aes_engine *e, int curve, const uint8_t *priva
     if (count == 0) return FPNN_AES_OK;
     DeviceGuard g(e->device);
     const size_t pb = (size_t)count * 2 * sl, kb = (size_t)count * keylen, ib = (size_t)count * 16;
-    int rc = grow(e, e->d_ecdh, e->cap_ecdh, pb + kb + ib + count);  // peers | keys | ivs | ok
+    int rc = e->ecdh.ensure(e, pb + kb + ib + count);  // peers | keys | ivs | ok
     if (rc) return rc;
-    uint8_t *d = e->d_ecdh;
+    uint8_t *d = e->ecdh.p;
     do {
         hipError_t err = hipMemcpyAsync(d, peer_public, pb, hipMemcpyHostToDevice, e->stream);
         if (err != hipSuccess) { rc = hip_fail(err, "ecdh upload"); break; }
@@ -2168,9 +2052,9 @@ int fpnn_ecdh_calc_key_host(fpnn_aes_engine *e, const char *curve, const uint8_t
     if (keylen != 16 && keylen != 32) return 0;
     if (!key || !iv) return FPNN_AES_ERR_ARG;
     DeviceGuard g(e->device);
-    int rc = grow(e, e->d_ecdh, e->cap_ecdh, 64 + 32 + 16 + 16);  // peer (<= 64) | key (32) | iv (16) | ok
+    int rc = e->ecdh.ensure(e, 64 + 32 + 16 + 16);  // peer (<= 64) | key (32) | iv (16) | ok
     if (rc) return rc;
-    uint8_t *d = e->d_ecdh;
+    uint8_t *d = e->ecdh.p;
     uint8_t res[32 + 16 + 1];
     do {
         hipError_t err = hipMemcpyAsync(d, peer_public, peer_len, hipMemcpyHostToDevice, e->stream);
@@ -2193,9 +2077,9 @@ int fpnn_ecdh_public_key_host(fpnn_aes_engine *e, int curve, const uint8_t *priv
     const int pl = fpnn_ecdh_private_len(curve), sl = fpnn_ecdh_secret_len(curve);
     if (pl < 0) return FPNN_AES_ERR_ARG;
     DeviceGuard g(e->device);
-    int rc = grow(e, e->d_ecdh, e->cap_ecdh, 32 + 64 + 16);  // private (<= 32) | public (<= 64) | ok
+    int rc = e->ecdh.ensure(e, 32 + 64 + 16);  // private (<= 32) | public (<= 64) | ok
     if (rc) return rc;
-    uint8_t *d = e->d_ecdh;
+    uint8_t *d = e->ecdh.p;
     uint8_t res[64 + 1];
     do {
         hipError_t err = hipMemcpyAsync(d, private_key, (size_t)pl, hipMemcpyHostToDevice, e->stream);

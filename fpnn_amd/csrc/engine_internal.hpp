@@ -25,6 +25,7 @@
 #include "numa_place.hpp"
 #include "aes_common.hpp"
 #include "kernels.hpp"
+#include "scratch_plan.hpp"
 
 namespace fpnn_aes {
 
@@ -222,7 +223,18 @@ struct HostActive {
     ~HostActive() { HostPool::g_host_active[d].fetch_sub(1, std::memory_order_relaxed); }
 };
 
+// One growing device buffer of the engine: pointer and capacity (elements); kZeroed: the whole
+// new capacity is zeroed on the stream when it grows.
+template <class T, bool kZeroed>
+struct Scratch {
+    T *p = nullptr;
+    uint64_t cap = 0;
+    int ensure(fpnn_aes_engine *e, uint64_t need);
+};
+
 }  // namespace fpnn_aes
+
+using fpnn_aes::RaggedPlan;  // (an element type of the scratch list)
 
 struct fpnn_aes_engine {
     int device = 0;
@@ -231,58 +243,18 @@ struct fpnn_aes_engine {
     int num_cus = 256;
     fpnn_aes::Variant variant;
     uint8_t *d_tables = nullptr;  // t0le[256] (1 KiB), sbox[256], td0le[256] (1 KiB), isbox[256]
-    // general-layout scratch
-    uint64_t *d_bstart = nullptr;
-    uint64_t cap_bstart = 0;
-    uint4 *d_boundary = nullptr;
-    uint64_t cap_boundary = 0;
-    uint4 *d_snap_iv = nullptr;  // stream-decrypt state snapshot
-    uint64_t cap_snap_iv = 0;
-    uint32_t *d_snap_pos = nullptr;
-    uint64_t cap_snap_pos = 0;
-    uint32_t *d_perm = nullptr;  // ragged encrypt: longest-first order
-    uint64_t cap_perm = 0;
-    uint32_t *d_buckets = nullptr;  // the length-order block (kLengthOrderWords; zeroed when grown, then
-    uint64_t cap_buckets = 0;       // zeroed again by its last reader, kernels.hpp)
-    uint64_t *d_fr_off = nullptr;  // package receive: absolute body offset per frame slot
-    uint64_t cap_fr_off = 0;
-    uint32_t *d_fr_slot = nullptr;  // package receive: key slot per frame slot
-    uint64_t cap_fr_slot = 0;
-    fpnn_aes::RaggedPlan *d_plan = nullptr;  // K1r: one entry per wave of the decrypt grid
-    uint64_t cap_plan = 0;
-    uint4 *d_sink = nullptr;  // K1r: 2 x uint4 per wave, stores of lanes with nothing to store
-    uint64_t cap_sink = 0;
-    uint64_t *d_desc_off = nullptr;  // K1r: materialized in_off / len of stride / uniform batches
-    uint64_t cap_desc_off = 0;
-    uint32_t *d_desc_len = nullptr;
-    uint64_t cap_desc_len = 0;
+    // growing scratch, one Scratch per line of scratch_plan.hpp's list: e->bstart.p, e->bstart.cap, ...
+#define X(name, type, zeroed) fpnn_aes::Scratch<type, zeroed> name;
+    FPNN_AES_SCRATCH_BUFFERS(X)
+#undef X
     uint64_t *d_total = nullptr;  // ragged block total (bstart[count]), device only
-    // *_frames decrypt (k_stream_frames.hip), per segment: the stream it belongs to, the
-    // stream's last non-empty frame before it, and the state K1r exports for it
-    uint32_t *d_sf_stream = nullptr;
-    uint64_t cap_sf_stream = 0;
-    uint32_t *d_sf_prev = nullptr;
-    uint64_t cap_sf_prev = 0;
-    uint4 *d_sf_iv = nullptr;
-    uint64_t cap_sf_iv = 0;
-    uint32_t *d_sf_pos = nullptr;
-    uint64_t cap_sf_pos = 0;
-    uint32_t *d_sf_slot = nullptr;  // the slot-addressed (_at) decrypt: every segment's key slot
-    uint64_t cap_sf_slot = 0;
-    uint64_t *d_lookback = nullptr;  // one-pass block map: tickets, epoch, tile status (zeroed when grown)
-    uint64_t cap_lookback = 0;
     // device-side consistency checks (kFault*): a pinned word kernels may set, read when the
     // stream is idle (fpnn_aes_engine_sync, synchronous calls) and reported as FPNN_AES_ERR_DEVICE
     uint32_t *h_fault = nullptr;
     uint32_t *d_fault = nullptr;
-    uint8_t *d_ecdh = nullptr;  // ECDH host forms / keyset / accept: peers | keys | ivs | ok (grown, kept; every
-                                // call zeroes what it used once its last reader is queued: ecdh_wipe)
-    uint64_t cap_ecdh = 0;
-    uint8_t *d_sstate = nullptr;  // stream host frames: (iv, pos) of the call's streams (grown, kept)
-    uint64_t cap_sstate = 0;
-    uint8_t *h_sstate = nullptr;  // its pinned twin
+    uint8_t *h_sstate = nullptr;  // the pinned twin of sstate
     uint64_t cap_hsstate = 0;
-    bool pools = false;            // stream-ordered allocation from `pool` for grow()
+    bool pools = false;            // stream-ordered allocation from `mpool` for the scratch
     hipMemPool_t mpool = nullptr;  // the engine's own memory pool (keeps freed scratch for reuse)
     std::vector<void *> deferred;  // grown-out scratch awaiting an idle stream (no pools)
     // K0 (k_small.hip): pinned staging of the small synchronous calls, its device view,
@@ -357,23 +329,35 @@ struct DeviceGuard {
 // With stream-ordered pools the old buffer is released by hipFreeAsync behind the work
 // already queued on this engine's stream; without them it is kept until the stream is
 // next idle (engine_sync, the end of a synchronous host call, engine_destroy).
-template <class T>
-int grow(fpnn_aes_engine *e, T *&ptr, uint64_t &cap, uint64_t need) {
+template <class T, bool kZeroed>
+int Scratch<T, kZeroed>::ensure(fpnn_aes_engine *e, uint64_t need) {
     if (need <= cap) return FPNN_AES_OK;
-    uint64_t n = cap ? cap : 1024;
-    while (n < need) n *= 2;
+    const uint64_t n = scratch_next_cap(cap, need);
     T *np = nullptr;
-    if (e->pools)
-        HIP_TRY(hipMallocFromPoolAsync(reinterpret_cast<void **>(&np), n * sizeof(T), e->mpool, e->stream));
-    else
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&np), n * sizeof(T)));
-    if (ptr) {
-        if (e->pools) HIP_TRY(hipFreeAsync(ptr, e->stream));
-        else e->deferred.push_back(ptr);
+    if (e->pools) HIP_TRY(hipMallocFromPoolAsync(reinterpret_cast<void **>(&np), n * sizeof(T), e->mpool, e->stream));
+    else HIP_TRY(hipMalloc(reinterpret_cast<void **>(&np), n * sizeof(T)));
+    if (p) {
+        if (e->pools) HIP_TRY(hipFreeAsync(p, e->stream));
+        else e->deferred.push_back(p);
     }
-    ptr = np;
+    p = np;
     cap = n;
+    if (kZeroed) HIP_TRY(hipMemsetAsync(p, 0, cap * sizeof(T), e->stream));
     return FPNN_AES_OK;
+}
+
+// every buffer to at least what `need` asks of it (scratch_plan.hpp: the need_* functions)
+inline int scratch_ensure(fpnn_aes_engine *e, const ScratchNeed &need) {
+    int rc = FPNN_AES_OK;
+#define X(name, type, zeroed) if (rc == FPNN_AES_OK) rc = e->name.ensure(e, need.n[SC_##name]);
+    FPNN_AES_SCRATCH_BUFFERS(X)
+#undef X
+    return rc;
+}
+
+// the device and kernel constants the scratch sizes depend on
+inline ScratchShape scratch_shape(const fpnn_aes_engine *e) {
+    return {(uint64_t)e->num_cus, kThreads / 64, block_map_small_max(), block_map_onepass_words, kLengthOrderWords};
 }
 
 // The engine's stream is idle: release grown-out scratch, and report (once) a consistency

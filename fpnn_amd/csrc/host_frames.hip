@@ -133,10 +133,10 @@ int slot_drain(fpnn_aes_engine *e, HostSlot &s, HostStats &st) {
     return FPNN_AES_OK;
 }
 
-// stream-state scratch of the host-frame calls: device (grow(): no free on the call path)
+// stream-state scratch of the host-frame calls: device (Scratch: no free on the call path)
 // and its pinned twin (grown only between calls' uses: the engine stream is drained)
 int sstate_reserve(fpnn_aes_engine *e, uint64_t bytes) {
-    if (int rc = grow(e, e->d_sstate, e->cap_sstate, bytes)) return rc;
+    if (int rc = e->sstate.ensure(e, bytes)) return rc;
     if (bytes > e->cap_hsstate) {
         uint64_t c = e->cap_hsstate ? e->cap_hsstate : 4096;
         while (c < bytes) c *= 2;
@@ -343,7 +343,7 @@ int host_pipeline(fpnn_aes_engine *e, bool encrypt, bool stream, const fpnn_aes_
     if (stream) {
         if (int rc = sstate_reserve(e, nseg * 20)) return rc;
         h_state = e->h_sstate;
-        d_state = e->d_sstate;
+        d_state = e->sstate.p;
         // (a fresh d_state is stream-ordered on the engine stream: the upload below waits for it)
         HIP_TRY(hipEventRecord(e->hs[0].kdone, e->stream));
         HIP_TRY(hipStreamWaitEvent(e->hs[0].st, e->hs[0].kdone, 0));
@@ -889,7 +889,7 @@ int mapped_stream_pipeline(fpnn_aes_engine *e, bool encrypt, const fpnn_aes_host
     if (int rc = mapped_begin(e)) return rc;
     // ---- the streams' (iv, pos), compact, on the device (engine stream) ----
     if (int rc = sstate_reserve(e, nseg * 20)) return rc;
-    uint8_t *h_state = e->h_sstate, *d_state = e->d_sstate;
+    uint8_t *h_state = e->h_sstate, *d_state = e->sstate.p;
     pack_stream_state(plan.segs, iv_state, pos_state, h_state);
     HIP_TRY(hipMemcpyAsync(d_state, h_state, nseg * 20, hipMemcpyHostToDevice, e->stream));
     // Chunks of FPNN_AES_MAP_CHUNK_MB (as the package path: the moves of chunk t overlap the
