@@ -129,6 +129,9 @@ SIGNATURES = {
                                     C.POINTER(C.c_size_t)]),
     "fpnn_aes_package_host": (C.c_int, [_vp, C.c_int, C.POINTER(HostFrame), C.c_uint32, _vp, C.c_uint32]),
     "fpnn_aes_stream_host": (C.c_int, [_vp, C.c_int, C.POINTER(HostFrame), C.c_uint32, _vp, _vp, _vp]),
+    "fpnn_aes_stream_host_at": (C.c_int, [_vp, C.c_int, C.POINTER(HostFrame), C.c_uint32, _vp, C.c_uint32, _vp, _vp]),
+    "fpnn_aes_stream_encrypt_at": (C.c_int, [_vp, C.POINTER(BatchDesc), _vp, C.c_uint32, _vp, _vp]),
+    "fpnn_aes_stream_decrypt_at": (C.c_int, [_vp, C.POINTER(BatchDesc), _vp, C.c_uint32, _vp, _vp]),
     "fpnn_aes_package_host_multi": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.POINTER(HostFrame), C.c_uint32,
                                               C.c_uint32]),
     "fpnn_aes_stream_host_multi": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.POINTER(HostFrame), C.c_uint32, _vp,

@@ -289,19 +289,50 @@ inline int audit_begin_keytable(fpnn_aes_engine *, const fpnn_aes_keyset *, KeyT
 inline int audit_end(fpnn_aes_engine *, int rc) { return rc; }
 #endif
 
-int run_encrypt_calls(fpnn_aes_engine *e, const fpnn_aes_batch *b, uint8_t *iv_state, uint32_t *pos_state, bool stream) {
+// The slot addressing of an _at call (fpnn_aes_stream_encrypt_at / _decrypt_at,
+// fpnn_aes_stream_*_frames_at, fpnn_aes_stream_recv_at): stream j's state AND key at
+// state_slot[j], checked against slot_bound on the device.
+// one_frame: no first_frame, stream j is segment j.
+struct SlotAddr {
+    const uint32_t *state_slot;
+    uint32_t slot_bound;
+    bool one_frame;
+};
+
+// what every _at call asks of its slot addressing: the slot names key and state, so there is no
+// second key addressing, and the bound never grows the table
+int check_slot_addr(const fpnn_aes_batch *b, uint64_t nstreams, const SlotAddr *at) {
+    if (b->key_slot || ((uintptr_t)at->state_slot & 3) || (nstreams && !at->state_slot)) return FPNN_AES_ERR_ARG;
+    if (at->slot_bound > table_slots(b->keys)) return FPNN_AES_ERR_ARG;
+    return FPNN_AES_OK;
+}
+
+// at (fpnn_aes_stream_encrypt_at, stream mode): the dispatch below is the same, and the kernel it
+// picks runs in its slot form (KEY_SLOT, k_stream_at.hip).
+int run_encrypt_calls(fpnn_aes_engine *e, const fpnn_aes_batch *b, uint8_t *iv_state, uint32_t *pos_state, bool stream,
+                      const SlotAddr *at = nullptr) {
     int rc = check_batch(e, b);
     if (rc) return rc;
     if (stream && b->count && (!iv_state || !pos_state || ((uintptr_t)iv_state & 15))) return FPNN_AES_ERR_ARG;
+    if (at && ((rc = check_slot_addr(b, b->count, at)) || ((uintptr_t)pos_state & 3))) return FPNN_AES_ERR_ARG;
     if (!stream && (b->flags & FPNN_AES_F_WIRE_PREFIX) && (b->out_off == nullptr && b->in == b->out))
         return FPNN_AES_ERR_ARG;  // the 4-byte prefix needs a distinct output layout
     if (!b->count) return FPNN_AES_OK;
     DeviceGuard g(e->device);
     const BatchScope batch_scope(e);  // (an early return clears the pending flag)
     KBatch k = make_kbatch(e, b, iv_state, pos_state);
-    if ((rc = audit_begin(e, b, iv_state, pos_state, k))) return rc;
+    if (at) {
+        k.state_slot = at->state_slot;
+        k.slot_bound = at->slot_bound;
+        k.slot_fault = e->d_fault;
+        // (the audit build: state arrays of slot_bound entries, state_slot[] of count)
+        const FrameTable f{nullptr, (uint32_t)b->count, at->slot_bound, e->d_fault, at->state_slot, nullptr};
+        if ((rc = audit_begin(e, b, iv_state, pos_state, k, &f))) return rc;
+    } else if ((rc = audit_begin(e, b, iv_state, pos_state, k))) {
+        return rc;
+    }
     const Layout layout = is_uniform_layout(b) ? LAYOUT_UNIFORM : LAYOUT_GENERAL;
-    const KeyMode km = (b->key_slot && b->keys->count > 1) ? KEY_LANE : KEY_UNIFORM;
+    const KeyMode km = at ? KEY_SLOT : (b->key_slot && b->keys->count > 1) ? KEY_LANE : KEY_UNIFORM;
     // Few chains (fewer than the lanes of a full chip) or ragged lengths: one quad per
     // chain (K2c); otherwise one lane per chain with 8-block chunks (K2).
     const uint64_t full_chip = (uint64_t)e->num_cus * kThreads;
@@ -326,15 +357,16 @@ int run_encrypt_calls(fpnn_aes_engine *e, const fpnn_aes_batch *b, uint8_t *iv_s
             // (everything that can fail is done before the length order is queued: its block is
             // left dirty until its last reader runs)
             if ((rc = scratch_ensure(e, need_encrypt_ragged(scratch_shape(e), b->count, hybrid)))) return rc;
-            if (stream) {  // bucket sizes read pos_state (the encrypt kernel reads it later)
-                k.pos_snap = pos_state;
-            }
+            // bucket sizes read pos_state (the encrypt kernel reads it later); the slot form
+            // orders by length alone (the position is the slot's: kernels.hpp)
+            const bool order_pos = stream && !at;
+            if (order_pos) k.pos_snap = pos_state;
             block = e->buckets.p;
             if (e->variant.poison_order > 0) {  // (tests) bucket counts left over as if by a lost call
                 e->variant.poison_order--;
                 HIP_TRY(hipMemsetAsync(block, 0x01, kWireFlagWord / 2 * sizeof(uint32_t), e->stream));
             }
-            HIP_TRY(launch_length_order(k, stream, e->perm.p, block, !hybrid, e->d_fault, e->stream));
+            HIP_TRY(launch_length_order(k, order_pos, e->perm.p, block, !hybrid, e->d_fault, e->stream));
             k.perm = e->perm.p;
         }
         EventPair *ev;
@@ -356,7 +388,10 @@ int run_encrypt_calls(fpnn_aes_engine *e, const fpnn_aes_batch *b, uint8_t *iv_s
                 h.long_bucket = 127;
                 h.quad_waves = 16;
             }
-            HIP_TRY(launch_encrypt_hybrid(k, h, b->keys->nrounds, km, stream, e->num_cus, e->stream));
+            if (at) HIP_TRY(launch_encrypt_hybrid_at(k, h, b->keys->nrounds, e->num_cus, e->stream));
+            else HIP_TRY(launch_encrypt_hybrid(k, h, b->keys->nrounds, km, stream, e->num_cus, e->stream));
+        } else if (at) {
+            HIP_TRY(launch_encrypt_coop_at(k, b->keys->nrounds, layout, sp.grid, sp.threads, e->stream));
         } else {
             HIP_TRY(launch_encrypt_coop(k, b->keys->nrounds, layout, km, stream, sp.grid, sp.threads, e->stream));
         }
@@ -375,13 +410,16 @@ int run_encrypt_calls(fpnn_aes_engine *e, const fpnn_aes_batch *b, uint8_t *iv_s
     if (k2_ragged && b->max_len <= kFrameMaxBytes)  // FPNN's quests: whole frames at once (K2s-DB)
         HIP_TRY(launch_encrypt_frames(k, b->keys->nrounds, km, (b->flags & FPNN_AES_F_WIRE_PREFIX) != 0,
                                       e->num_cus, e->stream));
+    else if (at)
+        HIP_TRY(launch_encrypt_chains_at(k, b->keys->nrounds, layout, sp.grid, sp.threads, e->stream));
     else
         HIP_TRY(launch_encrypt_chains(k, b->keys->nrounds, layout, km, stream, sp.grid, sp.threads, e->stream));
     return timing_end(e, ev, FPNN_AES_K_ENCRYPT);
 }
 
-int run_encrypt(fpnn_aes_engine *e, const fpnn_aes_batch *b, uint8_t *iv_state, uint32_t *pos_state, bool stream) {
-    return audit_end(e, run_encrypt_calls(e, b, iv_state, pos_state, stream));
+int run_encrypt(fpnn_aes_engine *e, const fpnn_aes_batch *b, uint8_t *iv_state, uint32_t *pos_state, bool stream,
+                const SlotAddr *at = nullptr) {
+    return audit_end(e, run_encrypt_calls(e, b, iv_state, pos_state, stream, at));
 }
 
 struct SnapCopy {  // what the single-workgroup block map's state copy reads and writes (stream batches)
@@ -508,15 +546,6 @@ int run_decrypt(fpnn_aes_engine *e, const fpnn_aes_batch *b, uint8_t *iv_state, 
 
 // ---- many frames per stream in one call (fpnn_aes_stream_*_frames, k_stream_frames.hip) ----
 
-// The slot addressing of an _at call (fpnn_aes_stream_*_frames_at, fpnn_aes_stream_recv_at):
-// stream j's state AND key at state_slot[j], checked against slot_bound on the device.
-// one_frame: recv_at -- no first_frame, stream j is segment j.
-struct SlotAddr {
-    const uint32_t *state_slot;
-    uint32_t slot_bound;
-    bool one_frame;
-};
-
 int check_frames(const fpnn_aes_engine *e, const fpnn_aes_batch *b, const uint32_t *first_frame, uint32_t nstreams,
                  const uint8_t *iv_state, const uint32_t *pos_state, const SlotAddr *at) {
     const int rc = check_batch(e, b);
@@ -526,11 +555,7 @@ int check_frames(const fpnn_aes_engine *e, const fpnn_aes_batch *b, const uint32
     if (nstreams && ((need_first && !first_frame) || !iv_state || !pos_state || ((uintptr_t)iv_state & 15) ||
                      ((uintptr_t)pos_state & 3) || ((uintptr_t)first_frame & 3)))
         return FPNN_AES_ERR_ARG;
-    if (at) {
-        // the slot names key and state: no second key addressing; the bound never grows the table
-        if (b->key_slot || ((uintptr_t)at->state_slot & 3) || (nstreams && !at->state_slot)) return FPNN_AES_ERR_ARG;
-        if (at->slot_bound > table_slots(b->keys)) return FPNN_AES_ERR_ARG;
-    }
+    if (at) return check_slot_addr(b, nstreams, at);
     return FPNN_AES_OK;
 }
 
@@ -622,6 +647,18 @@ int fpnn_aes::run_batch(fpnn_aes_engine *e, bool encrypt, const fpnn_aes_batch *
     return encrypt ? run_encrypt(e, b, iv_state, pos_state, stream) : run_decrypt(e, b, iv_state, pos_state, stream);
 }
 
+// One frame per stream by key-table slot (fpnn_aes_stream_encrypt_at / _decrypt_at).  Encrypt:
+// run_encrypt's stream dispatch, the kernel in its slot form.  Decrypt: the slot-addressed
+// *_frames path with a null frame table -- stream j is segment j -- as fpnn_aes_stream_recv_at.
+int fpnn_aes::run_batch_at(fpnn_aes_engine *e, bool encrypt, const fpnn_aes_batch *b, const uint32_t *state_slot,
+                           uint32_t slot_bound, uint8_t *iv_state, uint32_t *pos_state) {
+    if (b && (b->flags & FPNN_AES_F_WIRE_PREFIX)) return FPNN_AES_ERR_ARG;
+    const SlotAddr at{state_slot, slot_bound, true};
+    if (encrypt) return run_encrypt(e, b, iv_state, pos_state, true, &at);
+    if (!b) return FPNN_AES_ERR_ARG;
+    return run_frames(e, b, nullptr, b->count, iv_state, pos_state, false, &at);
+}
+
 // ===========================================================================
 // C-ABI
 
@@ -639,7 +676,8 @@ const char *fpnn_aes_version(void) {
            "state pre-pass + K1r); single calls <= 16 KiB: K0s resident server (K0 per launch); "
            "ECDH: one lane per derivation, special-prime folds as carry chains; "
            "live key table: keyset_set_keys / keyset_clear / ecdh_accept, one lane per slot, queued; "
-           "stream state by slot: stream_open / stream_close, stream_*_frames_at, stream_recv_at)";
+           "stream state by slot: stream_open / stream_close, stream_*_frames_at, stream_recv_at, "
+           "stream_encrypt_at / stream_decrypt_at (K2 / K2c / K2h slot forms), stream_host_at)";
 }
 
 int fpnn_aes_setup_encrypt(fpnn_aes_schedule *ctx, const uint8_t *key, size_t keylen) {
@@ -1206,6 +1244,16 @@ int fpnn_aes_stream_encrypt_frames(fpnn_aes_engine *e, const fpnn_aes_batch *b, 
 int fpnn_aes_stream_decrypt_frames(fpnn_aes_engine *e, const fpnn_aes_batch *b, const uint32_t *first_frame,
                                    uint32_t nstreams, uint8_t *iv_state, uint32_t *pos_state) {
     return run_frames(e, b, first_frame, nstreams, iv_state, pos_state, false);
+}
+
+int fpnn_aes_stream_encrypt_at(fpnn_aes_engine *e, const fpnn_aes_batch *b, const uint32_t *state_slot,
+                               uint32_t slot_bound, uint8_t *iv_state, uint32_t *pos_state) {
+    return run_batch_at(e, true, b, state_slot, slot_bound, iv_state, pos_state);
+}
+
+int fpnn_aes_stream_decrypt_at(fpnn_aes_engine *e, const fpnn_aes_batch *b, const uint32_t *state_slot,
+                               uint32_t slot_bound, uint8_t *iv_state, uint32_t *pos_state) {
+    return run_batch_at(e, false, b, state_slot, slot_bound, iv_state, pos_state);
 }
 
 int fpnn_aes_stream_encrypt_frames_at(fpnn_aes_engine *e, const fpnn_aes_batch *b, const uint32_t *first_frame,

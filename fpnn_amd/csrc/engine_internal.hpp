@@ -368,5 +368,9 @@ int stream_idle(fpnn_aes_engine *e);
 // stream entry points' common part
 int run_batch(fpnn_aes_engine *e, bool encrypt, const fpnn_aes_batch *b, uint8_t *iv_state, uint32_t *pos_state,
               bool stream);
+// the same for a stream batch of one frame per stream whose keys and (iv, pos) are addressed by
+// key-table slot: segment i at slot state_slot[i] of b->keys and of the device state arrays
+int run_batch_at(fpnn_aes_engine *e, bool encrypt, const fpnn_aes_batch *b, const uint32_t *state_slot,
+                 uint32_t slot_bound, uint8_t *iv_state, uint32_t *pos_state);
 
 }  // namespace fpnn_aes

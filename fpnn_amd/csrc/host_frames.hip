@@ -133,6 +133,14 @@ int slot_drain(fpnn_aes_engine *e, HostSlot &s, HostStats &st) {
     return FPNN_AES_OK;
 }
 
+// fpnn_aes_stream_host_at: frames[i].key_slot names a slot of the live key table, for the key
+// and for the state; iv_state / pos_state are then the DEVICE arrays fpnn_aes_stream_open wrote
+// (slot_bound entries), every chunk is ciphered by slot where the state lies (run_batch_at),
+// and the compact state block below is not used.
+struct HostAt {
+    uint32_t slot_bound;
+};
+
 // stream-state scratch of the host-frame calls: device (Scratch: no free on the call path)
 // and its pinned twin (grown only between calls' uses: the engine stream is drained)
 int sstate_reserve(fpnn_aes_engine *e, uint64_t bytes) {
@@ -317,14 +325,16 @@ int scatter_partner(fpnn_aes_engine *e, HostStats &hst, int k, HostSlot *&sc) {
 // they share the engine's scratch, and in stream mode a stream split across chunks
 // continues from the state the previous chunk left.
 int host_pipeline(fpnn_aes_engine *e, bool encrypt, bool stream, const fpnn_aes_host_frame *frames, uint32_t n,
-                  const fpnn_aes_keyset *keys, uint32_t flags, uint8_t *iv_state, uint32_t *pos_state) {
+                  const fpnn_aes_keyset *keys, uint32_t flags, uint8_t *iv_state, uint32_t *pos_state,
+                  const HostAt *at = nullptr) {
     const HostActive active_call(e->device);
     const uint64_t pre = (!stream && (flags & FPNN_AES_F_WIRE_PREFIX)) ? 4 : 0;
     // input bytes per pipeline chunk.  (Quarter-call chunks for small calls, so one IO
     // cycle's 8 MiB flush would overlap its steps, measured slower: 1.37 against 0.83 ms
     // per flush, each chunk's copies getting fewer threads, gpurun_out r05d.)
     const uint64_t kChunk = 32ull << 20;
-    StreamPlan plan(frames, stream ? n : 0, stream ? keys->count : 0);  // (package chunks walk `frames` directly)
+    // (package chunks walk `frames` directly)
+    StreamPlan plan(frames, stream ? n : 0, !stream ? 0 : at ? at->slot_bound : keys->count);
     if (stream && plan.segs.empty()) return FPNN_AES_OK;
     e->host_path = "host_staged";
     const uint64_t nseg = stream ? plan.segs.size() : n;
@@ -340,7 +350,7 @@ int host_pipeline(fpnn_aes_engine *e, bool encrypt, bool stream, const fpnn_aes_
     // ---- stream state: compact (iv, pos) of the touched streams on the device ----------
     uint8_t *d_state = nullptr, *h_state = nullptr;
     uint64_t chunk = kChunk, quota = 0;
-    if (stream) {
+    if (stream && !at) {
         if (int rc = sstate_reserve(e, nseg * 20)) return rc;
         h_state = e->h_sstate;
         d_state = e->sstate.p;
@@ -348,12 +358,14 @@ int host_pipeline(fpnn_aes_engine *e, bool encrypt, bool stream, const fpnn_aes_
         HIP_TRY(hipEventRecord(e->hs[0].kdone, e->stream));
         HIP_TRY(hipStreamWaitEvent(e->hs[0].st, e->hs[0].kdone, 0));
         pack_stream_state(plan.segs, iv_state, pos_state, h_state);
+    }
+    if (stream) {
         // bigger chunks for few long streams (more chain steps per launch), quota per
         // stream so one chunk spans as many streams as it can
         // (the mapped path keeps fixed chunks and a floor of 1024: the difference is kept on purpose)
         chunk = std::min<uint64_t>(256ull << 20, std::max<uint64_t>(kChunk, plan.left / 4));
         quota = std::max<uint64_t>(16u << 10, (chunk / nseg + 15) & ~15ull);
-        (void)hipMemcpyAsync(d_state, h_state, nseg * 20, hipMemcpyHostToDevice, e->hs[0].st);
+        if (!at) (void)hipMemcpyAsync(d_state, h_state, nseg * 20, hipMemcpyHostToDevice, e->hs[0].st);
     }
     int rc = FPNN_AES_OK;
     uint64_t si = 0;  // package: next frame
@@ -383,11 +395,16 @@ int host_pipeline(fpnn_aes_engine *e, bool encrypt, bool stream, const fpnn_aes_
         // (stream encrypt, every stream taking the same quota: a uniform batch skips the
         // ragged length ordering, MappedStream::batch)
         const ChunkLayout::Arrays d = c.arrays(s.d);
-        const fpnn_aes_batch b = chunk_batch(s.d, c.out_at, c.cnt, keys, pre, encrypt ? c.uniform : int64_t(-1),
-                                             d.in_off, pre ? d.out_off : nullptr, d.len, d.slot);
-        uint8_t *ivp = stream ? d_state + 16 * c.state0 : nullptr;
-        uint32_t *posp = stream ? reinterpret_cast<uint32_t *>(d_state + 16 * nseg) + c.state0 : nullptr;
-        rc = run_batch(e, encrypt, &b, ivp, posp, stream);
+        fpnn_aes_batch b = chunk_batch(s.d, c.out_at, c.cnt, keys, pre, encrypt ? c.uniform : int64_t(-1),
+                                       d.in_off, pre ? d.out_off : nullptr, d.len, d.slot);
+        if (at) {  // the chunk's slot array, uploaded with its descriptors, addresses key and state
+            b.key_slot = nullptr;
+            rc = run_batch_at(e, encrypt, &b, d.slot, at->slot_bound, iv_state, pos_state);
+        } else {
+            uint8_t *ivp = stream ? d_state + 16 * c.state0 : nullptr;
+            uint32_t *posp = stream ? reinterpret_cast<uint32_t *>(d_state + 16 * nseg) + c.state0 : nullptr;
+            rc = run_batch(e, encrypt, &b, ivp, posp, stream);
+        }
         if (rc) break;
         HIP_TRY(hipEventRecord(s.kdone, e->stream));
         HIP_TRY(hipStreamWaitEvent(s.st, s.kdone, 0));
@@ -401,7 +418,7 @@ int host_pipeline(fpnn_aes_engine *e, bool encrypt, bool stream, const fpnn_aes_
         const int r2 = slot_drain(e, sl, hst);
         if (!rc) rc = r2;
     }
-    if (stream) {
+    if (stream && !at) {
         if (!rc && ciphered) {
             const hipError_t err = hipMemcpy(h_state, d_state, nseg * 20, hipMemcpyDeviceToHost);
             if (err != hipSuccess) rc = hip_fail(err, "hipMemcpy(stream state)");
@@ -580,6 +597,10 @@ struct MapCipher {
     fpnn_aes_batch b;
     uint8_t *iv = nullptr;  // stream mode: the (iv, pos) the chunk's first segment continues from
     uint32_t *pos = nullptr;
+    // stream mode by slot (HostAt): iv / pos are the caller's device arrays of slot_bound
+    // entries, segment i's key and state at state_slot[i]
+    const uint32_t *state_slot = nullptr;
+    uint32_t slot_bound = 0;
 };
 
 // Chunk t of a mapped call: the host writes its descriptors into its slot's pinned block
@@ -674,7 +695,8 @@ int mapped_steps(fpnn_aes_engine *e, bool encrypt, HostStats &hst, Mode &mode) {
             MapSlot &m = e->ms[k1];
             HIP_TRY(hipStreamWaitEvent(e->stream, m.gathered, 0));
             const MapCipher x = mode.batch(m, ch[k1]);
-            rc = run_batch(e, encrypt, &x.b, x.iv, x.pos, x.iv != nullptr);
+            if (x.state_slot) rc = run_batch_at(e, encrypt, &x.b, x.state_slot, x.slot_bound, x.iv, x.pos);
+            else rc = run_batch(e, encrypt, &x.b, x.iv, x.pos, x.iv != nullptr);
             if (rc) break;
             HIP_TRY(hipEventRecord(m.ciphered, e->stream));
         }
@@ -805,6 +827,9 @@ struct MappedStream {
     bool encrypt;
     uint64_t chunk, quota;
     uint8_t *d_state;
+    const HostAt *at;                // by slot: the caller's device state arrays (d_state unused)
+    uint8_t *at_iv;
+    uint32_t *at_pos;
     std::vector<Piece> pieces;
     std::vector<ChunkSeg> cs;
 
@@ -870,6 +895,12 @@ struct MappedStream {
 
     MapCipher batch(const MapSlot &m, const MapChunk &c) const {
         const SegDesc sd(MoveDesc(m.d + c.desc_at, c.moves).end(), c.segs);
+        if (at) {
+            MapCipher x{chunk_batch(m.d, c.out_at, c.segs, keys, 0, c.uniform, sd.off, nullptr, sd.len, nullptr),
+                        at_iv, at_pos, sd.slot, at->slot_bound};
+            x.b.key_slot = nullptr;
+            return x;
+        }
         uint32_t *pos = reinterpret_cast<uint32_t *>(d_state + 16 * plan.segs.size());
         return {chunk_batch(m.d, c.out_at, c.segs, keys, 0, c.uniform, sd.off, nullptr, sd.len, sd.slot),
                 d_state + 16 * c.state0, pos + c.state0};
@@ -877,21 +908,25 @@ struct MappedStream {
 };
 
 int mapped_stream_pipeline(fpnn_aes_engine *e, bool encrypt, const fpnn_aes_host_frame *frames, uint32_t n,
-                           const fpnn_aes_keyset *keys, const MapView &v, uint8_t *iv_state, uint32_t *pos_state) {
+                           const fpnn_aes_keyset *keys, const MapView &v, uint8_t *iv_state, uint32_t *pos_state,
+                           const HostAt *at = nullptr) {
     const HostActive active_call(e->device);
     HostStats hst;
     const double t_call = hst.on ? HostStats::now() : 0;
-    StreamPlan plan(frames, n, keys->count);  // streams in array order
+    StreamPlan plan(frames, n, at ? at->slot_bound : keys->count);  // streams in array order
     if (plan.segs.empty()) return FPNN_AES_OK;
     const uint64_t nseg = plan.segs.size();
     const double t_sorted = hst.on ? HostStats::now() : 0;
     DeviceGuard g(e->device);
     if (int rc = mapped_begin(e)) return rc;
     // ---- the streams' (iv, pos), compact, on the device (engine stream) ----
-    if (int rc = sstate_reserve(e, nseg * 20)) return rc;
-    uint8_t *h_state = e->h_sstate, *d_state = e->sstate.p;
-    pack_stream_state(plan.segs, iv_state, pos_state, h_state);
-    HIP_TRY(hipMemcpyAsync(d_state, h_state, nseg * 20, hipMemcpyHostToDevice, e->stream));
+    uint8_t *h_state = nullptr, *d_state = nullptr;
+    if (!at) {
+        if (int rc = sstate_reserve(e, nseg * 20)) return rc;
+        h_state = e->h_sstate, d_state = e->sstate.p;
+        pack_stream_state(plan.segs, iv_state, pos_state, h_state);
+        HIP_TRY(hipMemcpyAsync(d_state, h_state, nseg * 20, hipMemcpyHostToDevice, e->stream));
+    }
     // Chunks of FPNN_AES_MAP_CHUNK_MB (as the package path: the moves of chunk t overlap the
     // cipher of chunk t - 1, so more, smaller chunks pipeline better than a few large ones),
     // each taking a quota from as many streams as fit: the encrypt of a chunk is one serial
@@ -899,9 +934,9 @@ int mapped_stream_pipeline(fpnn_aes_engine *e, bool encrypt, const fpnn_aes_host
     // (the staged path grows its chunks and keeps a floor of 16 Ki: the difference is kept on purpose)
     const uint64_t chunk = map_chunk_bytes();
     const uint64_t quota = std::max<uint64_t>(1024, (chunk / nseg + 15) & ~15ull);
-    MappedStream mode{e, frames, keys, v, plan, encrypt, chunk, quota, d_state};
+    MappedStream mode{e, frames, keys, v, plan, encrypt, chunk, quota, d_state, at, iv_state, pos_state};
     const int rc = mapped_steps(e, encrypt, hst, mode);
-    if (!rc) {
+    if (!rc && !at) {
         HIP_TRY(hipMemcpy(h_state, d_state, nseg * 20, hipMemcpyDeviceToHost));
         unpack_stream_state(plan.segs, h_state, iv_state, pos_state);
     }
@@ -1003,6 +1038,31 @@ int fpnn_aes_stream_host(fpnn_aes_engine *e, int encrypt, const fpnn_aes_host_fr
             return mapped_stream_pipeline(e, encrypt != 0, frames, n, keys, v, iv_state, pos_state);
     }
     return host_pipeline(e, encrypt != 0, true, frames, n, keys, 0, iv_state, pos_state);
+}
+
+// Stream-mode host frames of connections that live in the key table on the device: key and
+// (iv, pos) by table slot, the state in the device arrays fpnn_aes_stream_open wrote.  The host
+// knows every slot, so a bad one fails here, before anything is queued or touched.
+int fpnn_aes_stream_host_at(fpnn_aes_engine *e, int encrypt, const fpnn_aes_host_frame *frames, uint32_t n,
+                            const fpnn_aes_keyset *keys, uint32_t slot_bound, uint8_t *iv_state, uint32_t *pos_state) {
+    if (!e || !keys || (n && !frames)) return FPNN_AES_ERR_ARG;
+    if (keys->device != e->device || keys->count == 0) return FPNN_AES_ERR_ARG;
+    if (slot_bound > fpnn_aes_keyset_capacity(keys)) return FPNN_AES_ERR_ARG;
+    for (uint32_t i = 0; i < n; i++)
+        if ((frames[i].len && (!frames[i].src || !frames[i].dst)) || frames[i].key_slot >= slot_bound)
+            return FPNN_AES_ERR_ARG;
+    if (int rc = debug_fail_point()) return rc;
+    if (n && (!iv_state || !pos_state || ((uintptr_t)iv_state & 15) || ((uintptr_t)pos_state & 3)))
+        return FPNN_AES_ERR_ARG;
+    if (!n) return FPNN_AES_OK;
+    const HostAt at{slot_bound};
+    if (mapped_enabled()) {  // every frame in registered host memory: the GPU moves the bytes
+        MapView v;
+        if (int rc = map_view(e->device, v)) return rc;
+        if (!v.lo.empty() && first_unmapped(e, v, frames, n, 0) == n)  // (stream frames depend on each other)
+            return mapped_stream_pipeline(e, encrypt != 0, frames, n, keys, v, iv_state, pos_state, &at);
+    }
+    return host_pipeline(e, encrypt != 0, true, frames, n, keys, 0, iv_state, pos_state, &at);
 }
 
 // ---- one host batch over several engines (GPUs) ------------------------------------------

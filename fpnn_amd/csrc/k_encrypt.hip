@@ -15,6 +15,7 @@ namespace fpnn_aes {
 
 template <int NR, int LAYOUT, int KM, bool STREAM, int NT, int CH, bool FENCE = false>
 __global__ __launch_bounds__(kThreads, 4 * Lds<NT>::kBlocksPerCU) void k_cfb_encrypt_chains(KBatch b) {
+    static_assert(KM != KEY_SLOT || STREAM, "the slot form is a stream form");
     __shared__ uint4 lds4[Lds<NT>::kBytes / 16];
     lds_fill_tables<NT>(lds4, b.t0le);
     __syncthreads();
@@ -40,23 +41,28 @@ __global__ __launch_bounds__(kThreads, 4 * Lds<NT>::kBlocksPerCU) void k_cfb_enc
     uint32_t rk_slot = ~0u;
     for (uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; s < b.count; s += nthreads) {
         const Seg g = get_seg<LAYOUT>(b, s);
+        // KEY_SLOT: the chain's key-table slot, read once, names its key and its state entry
+        // (it stays live as rk_slot); a slot past the bound: the chain is not run
+        uint32_t slot = g.slot;
+        if (KM == KEY_SLOT && !seg_state_slot(b, s, slot)) continue;
+        const uint64_t si = KM == KEY_SLOT ? (uint64_t)slot : s;  // the chain's state entry
         FA_DECL(a_ilo = (uintptr_t)g.in, a_ihi = (uintptr_t)g.in + g.len, a_olo = (uintptr_t)g.out,
                 a_ohi = (uintptr_t)g.out + g.len + ((b.flags & F_WIRE_PREFIX) ? 4u : 0u));
-        const DevKey *key = FA_AT(b, AB_KEYS, b.keys + (KM == KEY_UNIFORM ? 0u : g.slot), sizeof(DevKey));
+        const DevKey *key = FA_AT(b, AB_KEYS, b.keys + (KM == KEY_UNIFORM ? 0u : slot), sizeof(DevKey));
         if (KM == KEY_UNIFORM) {
             rk = rku;
-        } else if (g.slot != rk_slot) {
+        } else if (slot != rk_slot) {
             rk = load_round_keys<NR>(key);
-            rk_slot = g.slot;
+            rk_slot = slot;
         }
         uint4 eiv = eiv_u;
-        if (kFirst && KM != KEY_UNIFORM && use_eiv) eiv = *FA_AT(b, AB_EIV, b.eiv + g.slot, 16);
+        if (kFirst && KM != KEY_UNIFORM && use_eiv) eiv = *FA_AT(b, AB_EIV, b.eiv + slot, 16);
 
         uint4 iv;
         uint32_t n = 0;
         if (STREAM) {
-            iv = ld_state_iv(FA_AT(b, AB_IV_STATE, b.iv_state + 16 * s, 16));
-            n = *FA_AT(b, AB_POS_STATE, b.pos_state + s, 4);
+            iv = ld_state_iv(FA_AT(b, AB_IV_STATE, b.iv_state + 16 * si, 16));
+            n = *FA_AT(b, AB_POS_STATE, b.pos_state + si, 4);
         } else {
             iv = *reinterpret_cast<const uint4 *>(key->iv);
         }
@@ -88,7 +94,7 @@ __global__ __launch_bounds__(kThreads, 4 * Lds<NT>::kBlocksPerCU) void k_cfb_enc
         const uint32_t nfull = rem >> 4;
         uint32_t i = 0;
         // Per-lane AES-256 round keys (60 VGPRs) leave room for 4-block chunks only.
-        constexpr int C = (KM == KEY_LANE && NR == 14 && CH > 4) ? 4 : CH;
+        constexpr int C = (KM != KEY_UNIFORM && NR == 14 && CH > 4) ? 4 : CH;
         if (C > 1 && (b.flags & F_ALIGN_CHUNKS)) {
             // a 16-B aligned segment that starts inside a 128-B line (1472-B datagrams:
             // every other one) runs its first blocks singly, so every chunk below reads
@@ -163,8 +169,8 @@ __global__ __launch_bounds__(kThreads, 4 * Lds<NT>::kBlocksPerCU) void k_cfb_enc
             n = rem;
         }
         if (STREAM) {
-            *reinterpret_cast<uint4 *>(FA_AT(b, AB_IV_STATE, b.iv_state + 16 * s, 16)) = iv;
-            *FA_AT(b, AB_POS_STATE, b.pos_state + s, 4) = n;
+            *reinterpret_cast<uint4 *>(FA_AT(b, AB_IV_STATE, b.iv_state + 16 * si, 16)) = iv;
+            *FA_AT(b, AB_POS_STATE, b.pos_state + si, 4) = n;
         }
     }
 }
@@ -440,6 +446,7 @@ __global__ __launch_bounds__(256 * OCC) __attribute__((amdgpu_waves_per_eu(OCC, 
 
 template <int NR, int LAYOUT, int KM, bool STREAM, int NT>
 __global__ __launch_bounds__(kThreads, 4) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_cfb_encrypt_coop(KBatch b) {
+    static_assert(KM != KEY_SLOT || STREAM, "the slot form is a stream form");
     __shared__ uint4 lds4[Lds<NT>::kBytes / 16];
     lds_fill_tables<NT>(lds4, b.t0le);
     __syncthreads();
@@ -451,9 +458,14 @@ __global__ __launch_bounds__(kThreads, 4) __attribute__((amdgpu_waves_per_eu(4, 
     for (uint64_t t = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 2; t < b.count; t += nquads) {
         const uint64_t s = b.perm ? min(*FA_AT(b, AB_PERM, b.perm + t, 4), (uint32_t)b.count - 1u) : t;  // longest chains first (ragged batches)
         const Seg g = get_seg<LAYOUT>(b, s);
+        // KEY_SLOT: the chain's key-table slot, read once, names its key and its state entry;
+        // a slot past the bound: the chain is not run
+        uint32_t slot = g.slot;
+        if (KM == KEY_SLOT && !seg_state_slot(b, s, slot)) continue;
+        const uint64_t si = KM == KEY_SLOT ? (uint64_t)slot : s;  // the chain's state entry
         FA_DECL(a_ilo = (uintptr_t)g.in, a_ihi = (uintptr_t)g.in + g.len, a_olo = (uintptr_t)g.out,
                 a_ohi = (uintptr_t)g.out + g.len + ((b.flags & F_WIRE_PREFIX) ? 4u : 0u));
-        const DevKey *key = FA_AT(b, AB_KEYS, b.keys + (KM == KEY_UNIFORM ? 0u : g.slot), sizeof(DevKey));
+        const DevKey *key = FA_AT(b, AB_KEYS, b.keys + (KM == KEY_UNIFORM ? 0u : slot), sizeof(DevKey));
         uint32_t rkq[NR + 1];
 #pragma unroll
         for (int r = 0; r <= NR; r++) rkq[r] = key->rk[4 * r + q];
@@ -465,12 +477,12 @@ __global__ __launch_bounds__(kThreads, 4) __attribute__((amdgpu_waves_per_eu(4, 
         const bool use_eiv = !STREAM && b.eiv != nullptr;
         uint32_t ew = 0;  // this lane's word of E_k(IV)
         if (STREAM) {
-            iv = reinterpret_cast<const uint32_t *>(FA_AT(b, AB_IV_STATE, b.iv_state + 16 * s, 16))[q];
-            n = *FA_AT(b, AB_POS_STATE, b.pos_state + s, 4);
+            iv = reinterpret_cast<const uint32_t *>(FA_AT(b, AB_IV_STATE, b.iv_state + 16 * si, 16))[q];
+            n = *FA_AT(b, AB_POS_STATE, b.pos_state + si, 4);
         } else {
             iv = reinterpret_cast<const uint32_t *>(key->iv)[q];
             if (use_eiv)
-                ew = reinterpret_cast<const uint32_t *>(FA_AT(b, AB_EIV, b.eiv + (KM == KEY_UNIFORM ? 0u : g.slot), 16))[q];
+                ew = reinterpret_cast<const uint32_t *>(FA_AT(b, AB_EIV, b.eiv + (KM == KEY_UNIFORM ? 0u : slot), 16))[q];
         }
         const uint8_t *p = g.in;
         uint8_t *o = g.out;
@@ -566,14 +578,17 @@ __global__ __launch_bounds__(kThreads, 4) __attribute__((amdgpu_waves_per_eu(4, 
             n = rem;
         }
         if (STREAM) {
-            reinterpret_cast<uint32_t *>(FA_AT(b, AB_IV_STATE, b.iv_state + 16 * s, 16))[q] = iv;
-            if (q == 0) *FA_AT(b, AB_POS_STATE, b.pos_state + s, 4) = n;
+            reinterpret_cast<uint32_t *>(FA_AT(b, AB_IV_STATE, b.iv_state + 16 * si, 16))[q] = iv;
+            if (q == 0) *FA_AT(b, AB_POS_STATE, b.pos_state + si, 4) = n;
         }
     }
 }
 
 // ---------------------------------------------------------------------------
-// Launchers (runtime -> template dispatch)
+// Launchers (runtime -> template dispatch).  k_stream_at.hip includes this file for the kernel
+// templates alone (FPNN_AES_KERNEL_TEMPLATES_ONLY) and instantiates their slot forms in a
+// code object of its own, so this file's code object holds what it always held.
+#ifndef FPNN_AES_KERNEL_TEMPLATES_ONLY
 
 // Which K2 runs (the other sides of these choices were measured slower and removed in
 // round 6, their A/B switches with them):
@@ -700,5 +715,6 @@ hipError_t launch_encrypt_chains(const KBatch &b, int nrounds, Layout layout, Ke
     }
     return hipGetLastError();
 }
+#endif  // FPNN_AES_KERNEL_TEMPLATES_ONLY
 
 }  // namespace fpnn_aes

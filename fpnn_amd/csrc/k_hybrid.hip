@@ -52,6 +52,7 @@ __device__ __forceinline__ uint32_t lane_rank(uint64_t mask) {  // set bits of m
 template <int NR, int KM, bool STREAM, int NT, int CH, bool SHIFT, bool FENCE, bool LANES = true>
 __global__ __launch_bounds__(kThreads, 4) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_cfb_encrypt_hybrid(KBatch b, HybridArgs h) {
     static_assert(!(SHIFT && LANES), "wire frames run on quads alone");
+    static_assert(KM != KEY_SLOT || STREAM, "the slot form is a stream form");
     __shared__ uint4 lds4[Lds<NT>::kBytes / 16];
     lds_fill_tables<NT>(lds4, b.t0le);
     __syncthreads();
@@ -123,7 +124,19 @@ __global__ __launch_bounds__(kThreads, 4) __attribute__((amdgpu_waves_per_eu(4, 
         auto begin = [&](uint64_t t) {
             const uint64_t s = min(*FA_AT(b, AB_PERM, b.perm + t, 4), (uint32_t)b.count - 1u);  // (in range even from a bad block)
             sid = s;
-            const Seg g = get_seg<LAYOUT_GENERAL>(b, s);
+            Seg g = get_seg<LAYOUT_GENERAL>(b, s);
+            if (KM == KEY_SLOT) {
+                // the chain's key-table slot, read once: its key and, as sid, its state entry.  A
+                // slot past the bound runs as an empty chain under slot 0's key from a zero
+                // state -- no byte is read or written -- and finish() leaves its state alone
+                // (sid keeps the bad slot: nothing extra is live across the rounds)
+                const bool live = seg_state_slot(b, s, g.slot);
+                sid = g.slot;
+                if (!live) {
+                    g.slot = 0u;
+                    g.len = 0u;
+                }
+            }
             FA_SET(a_ilo, (uintptr_t)g.in);
             FA_SET(a_ihi, (uintptr_t)g.in + g.len);
             FA_SET(a_olo, (uintptr_t)g.out);
@@ -134,9 +147,12 @@ __global__ __launch_bounds__(kThreads, 4) __attribute__((amdgpu_waves_per_eu(4, 
                 for (int r = 0; r <= NR; r++) rkq[r] = key->rk[4 * r + q];
             }
             uint32_t v, pos;
-            if (STREAM) {
-                v = reinterpret_cast<const uint32_t *>(FA_AT(b, AB_IV_STATE, b.iv_state + 16 * s, 16))[q];
-                pos = *FA_AT(b, AB_POS_STATE, b.pos_state + s, 4);
+            if (STREAM && KM == KEY_SLOT && sid >= b.slot_bound) {
+                v = 0u;
+                pos = 0u;
+            } else if (STREAM) {
+                v = reinterpret_cast<const uint32_t *>(FA_AT(b, AB_IV_STATE, b.iv_state + 16 * sid, 16))[q];
+                pos = *FA_AT(b, AB_POS_STATE, b.pos_state + sid, 4);
             } else {
                 v = reinterpret_cast<const uint32_t *>(key->iv)[q];
                 pos = 0;
@@ -227,7 +243,7 @@ __global__ __launch_bounds__(kThreads, 4) __attribute__((amdgpu_waves_per_eu(4, 
                 }
                 n = tail;
             }
-            if (STREAM) {
+            if (STREAM && (KM != KEY_SLOT || sid < b.slot_bound)) {
                 reinterpret_cast<uint32_t *>(FA_AT(b, AB_IV_STATE, b.iv_state + 16 * sid, 16))[q] = iv;
                 if (q == 0) *FA_AT(b, AB_POS_STATE, b.pos_state + sid, 4) = n;
             }
@@ -402,16 +418,27 @@ __global__ __launch_bounds__(kThreads, 4) __attribute__((amdgpu_waves_per_eu(4, 
         auto begin = [&](uint64_t t) {
             const uint64_t s = min(*FA_AT(b, AB_PERM, b.perm + t, 4), (uint32_t)b.count - 1u);  // (in range even from a bad block)
             sid = s;
-            const Seg g = get_seg<LAYOUT_GENERAL>(b, s);
+            Seg g = get_seg<LAYOUT_GENERAL>(b, s);
+            if (KM == KEY_SLOT) {  // as in the quad session: sid = the slot, a bad one runs as an empty chain
+                const bool live = seg_state_slot(b, s, g.slot);
+                sid = g.slot;
+                if (!live) {
+                    g.slot = 0u;
+                    g.len = 0u;
+                }
+            }
             FA_SET(a_ilo, (uintptr_t)g.in);
             FA_SET(a_ihi, (uintptr_t)g.in + g.len);
             FA_SET(a_olo, (uintptr_t)g.out);
             FA_SET(a_ohi, (uintptr_t)g.out + g.len);
             const DevKey *key = FA_AT(b, AB_KEYS, b.keys + (KM == KEY_UNIFORM ? 0u : g.slot), sizeof(DevKey));
             if (KM != KEY_UNIFORM) rkl = load_round_keys<NR>(key);
-            if (STREAM) {
-                iv = ld_state_iv(FA_AT(b, AB_IV_STATE, b.iv_state + 16 * s, 16));
-                n = *FA_AT(b, AB_POS_STATE, b.pos_state + s, 4);
+            if (STREAM && KM == KEY_SLOT && sid >= b.slot_bound) {
+                iv = make_uint4(0, 0, 0, 0);
+                n = 0;
+            } else if (STREAM) {
+                iv = ld_state_iv(FA_AT(b, AB_IV_STATE, b.iv_state + 16 * sid, 16));
+                n = *FA_AT(b, AB_POS_STATE, b.pos_state + sid, 4);
             } else {
                 iv = *reinterpret_cast<const uint4 *>(key->iv);
                 n = 0;
@@ -458,7 +485,7 @@ __global__ __launch_bounds__(kThreads, 4) __attribute__((amdgpu_waves_per_eu(4, 
                         iv = select_bytes(byte_mask(0, (int)tail), c, ks);
                         n = tail;
                     }
-                    if (STREAM) {
+                    if (STREAM && (KM != KEY_SLOT || sid < b.slot_bound)) {
                         *reinterpret_cast<uint4 *>(FA_AT(b, AB_IV_STATE, b.iv_state + 16 * sid, 16)) = iv;
                         *FA_AT(b, AB_POS_STATE, b.pos_state + sid, 4) = n;
                     }
@@ -489,7 +516,7 @@ __global__ __launch_bounds__(kThreads, 4) __attribute__((amdgpu_waves_per_eu(4, 
             const uint32_t kk2 = rest < (uint32_t)CH ? rest : (uint32_t)CH;
             // next step's blocks are loaded during this one's rounds (PF), except where the
             // registers are short (per-lane AES-192/256 round keys)
-            constexpr bool PF = !(KM == KEY_LANE && NR >= 12);
+            constexpr bool PF = !(KM != KEY_UNIFORM && NR >= 12);
             if (fresh || !PF) {
 #pragma unroll
                 for (int j = 0; j < CH; j++) a[j] = j < (int)kk ? load16(FA_SEG(b, AB_IN, p + 16 * j, 16, a_ilo, a_ihi)) : a[j];
@@ -535,6 +562,9 @@ __global__ __launch_bounds__(kThreads, 4) __attribute__((amdgpu_waves_per_eu(4, 
     length_order_release(h.ctr - kTicketWords);  // the block's last reader: zero it for the next call
 }
 
+// (k_stream_at.hip includes this file for the kernel template alone and instantiates its slot
+// form in a code object of its own: k_encrypt.hip, "Launchers")
+#ifndef FPNN_AES_KERNEL_TEMPLATES_ONLY
 template <int NR>
 static void hybrid_nr(const KBatch &b, const HybridArgs &h, KeyMode km, bool stream, int grid, hipStream_t st) {
 #define FPNN_HYB(K, STR, CH, SH, LN) \
@@ -567,5 +597,6 @@ hipError_t launch_encrypt_hybrid(const KBatch &b, const HybridArgs &h, int nroun
     }
     return hipGetLastError();
 }
+#endif  // FPNN_AES_KERNEL_TEMPLATES_ONLY
 
 }  // namespace fpnn_aes

@@ -32,10 +32,26 @@ struct KBatch {
     // block map (decrypt)
     uint64_t total_blocks;   // uniform layout: exact; general: copy of *total_ptr
     uint32_t nb_uniform;     // uniform layout: blocks per segment
-    uint32_t runs;           // K1r: interior runs on (Variant::k1r_runs)
+    // The slot form of the stream encrypt kernels (KEY_SLOT, fpnn_aes_stream_encrypt_at) reads no
+    // block map; its three arguments share the storage of three block-map fields, so the kernel
+    // argument of every other kernel keeps its layout:
+    //   state_slot[s]  segment s's key-table slot: its key is keys[state_slot[s]] and its state
+    //                  entry state_slot[s] of iv_state / pos_state (key_slot is null)
+    //   slot_bound     entries of the state arrays (at most the table's slots)
+    //   slot_fault     gets kFaultKeySlot when a state_slot[] entry lies at or past slot_bound
+    union {
+        uint32_t runs;       // K1r: interior runs on (Variant::k1r_runs)
+        uint32_t slot_bound;
+    };
     uint64_t magic;          // ceil(2^64 / nb_uniform)
-    const uint64_t *bstart;  // general: first virtual block of each segment (count + 1)
-    const uint4 *boundary;   // in-place: Cx block preceding each 64-block chunk
+    union {
+        const uint64_t *bstart;  // general: first virtual block of each segment (count + 1)
+        const uint32_t *state_slot;
+    };
+    union {
+        const uint4 *boundary;   // in-place: Cx block preceding each 64-block chunk
+        uint32_t *slot_fault;
+    };
     // stream decrypt: the (iv, pos) state as it was when the call was queued.  The
     // kernel writes the new state into iv_state/pos_state while other waves may still
     // be reading the old one, so every read goes to this snapshot.
@@ -57,7 +73,9 @@ struct KBatch {
 // uniform_len % 1024 == 0, else K1k).
 // GENERAL: offset/length/slot arrays (decrypt: K1r, k_ragged.hip).
 enum Layout { LAYOUT_UNIFORM = 0, LAYOUT_GENERAL = 1, LAYOUT_FULL = 2 };
-enum KeyMode { KEY_UNIFORM = 0, KEY_LANE = 1 };
+// KEY_SLOT (stream encrypt only): per-lane keys as KEY_LANE, and the segment's (iv, pos)
+// lives at its key slot -- KBatch::state_slot; launch_encrypt_*_at below.
+enum KeyMode { KEY_UNIFORM = 0, KEY_LANE = 1, KEY_SLOT = 2 };
 
 // Per-engine dispatch settings that tests set (tests/conftest.py) so that small batches
 // reach every session of the shipped kernels.  Round 4 removed the measured-and-rejected
@@ -196,6 +214,16 @@ struct HybridArgs {
 };
 hipError_t launch_encrypt_hybrid(const KBatch &b, const HybridArgs &h, int nrounds, KeyMode km, bool stream, int grid,
                                  hipStream_t st);
+// The slot forms of K2, K2c and K2h's stream paths (k_stream_at.hip, instantiated from the same
+// kernel templates with KEY_SLOT; fpnn_aes_stream_encrypt_at): b.state_slot / b.slot_bound /
+// b.slot_fault set, b.key_slot null, b.iv_state / b.pos_state of slot_bound entries.  A segment
+// whose slot lies at or past the bound is reported (kFaultKeySlot): neither state is touched and
+// no byte of it is written.  K2h's length order for these calls is by length alone (the
+// engine queues launch_length_order with stream = false: the carried position, at most 15
+// bytes, would have to be gathered through the slot).
+hipError_t launch_encrypt_chains_at(const KBatch &b, int nrounds, Layout layout, int grid, int threads, hipStream_t st);
+hipError_t launch_encrypt_coop_at(const KBatch &b, int nrounds, Layout layout, int grid, int threads, hipStream_t st);
+hipError_t launch_encrypt_hybrid_at(const KBatch &b, const HybridArgs &h, int nrounds, int grid, hipStream_t st);
 // length bucket of a block count (descending: bucket 0 = longest), as launch_length_order
 uint32_t length_bucket_of(uint64_t nblocks);
 // Ragged batches: perm[] = segment indices ordered by block count, longest first

@@ -44,6 +44,17 @@ __device__ __forceinline__ Seg get_seg(const KBatch &b, uint64_t s) {
     return g;
 }
 
+// KEY_SLOT kernels: segment s's key-table slot, which names its key and its state entry.
+// false: the slot lies at or past b.slot_bound -- reported (kFaultKeySlot); the caller then
+// touches neither the key table nor the state for this segment and writes none of its bytes
+// (the contract of stream_slot(), k_stream_frames.hip).
+__device__ __forceinline__ bool seg_state_slot(const KBatch &b, uint64_t s, uint32_t &sl) {
+    sl = *FA_AT(b, AB_STATE_SLOT, b.state_slot + s, 4);
+    if (sl < b.slot_bound) return true;
+    if (b.slot_fault) __hip_atomic_fetch_or(b.slot_fault, kFaultKeySlot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    return false;
+}
+
 __device__ __forceinline__ uint4 ld_state_iv(const uint8_t *p) { return *reinterpret_cast<const uint4 *>(p); }
 
 // Virtual (stream-aligned) block `bi` of a segment that starts at CFB position n0:

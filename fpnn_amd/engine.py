@@ -236,6 +236,28 @@ class Engine:
         check(lib.fpnn_aes_stream_host(self._h, int(encrypt), arr, n, keys.handle,
                                        iv_state.ctypes.data, pos_state.ctypes.data), "stream_host")
 
+    def stream_host_at(self, encrypt: bool, frames, keys: "KeySet", slot_bound: int, iv_state: torch.Tensor,
+                       pos_state: torch.Tensor):
+        """fpnn_aes_stream_host_at: stream-mode host frames of connections that live in the key
+        table.  frames: sequence of (src, dst, slot) numpy views, or a structured array with
+        HOST_FRAME_DTYPE; slot names the key AND the state entry.  iv_state / pos_state: the DEVICE
+        arrays KeySet.stream_open wrote (slot_bound entries), updated in place."""
+        if iv_state.numel() < 16 * slot_bound or pos_state.numel() < slot_bound:
+            raise ValueError("state arrays must hold slot_bound entries")
+        if isinstance(frames, np.ndarray):
+            n = len(frames)
+            arr = C.cast(C.c_void_p(frames.ctypes.data), C.POINTER(HostFrame))
+        else:
+            n = len(frames)
+            arr = (HostFrame * max(1, n))()
+            for i, (src, dst, slot) in enumerate(frames):
+                arr[i].src = src.ctypes.data if src.size else None
+                arr[i].dst = dst.ctypes.data if dst.size else None
+                arr[i].len = src.size
+                arr[i].key_slot = slot
+        check(lib.fpnn_aes_stream_host_at(self._h, int(encrypt), arr, n, keys.handle, slot_bound, _ptr(iv_state),
+                                          _ptr(pos_state)), "stream_host_at")
+
     # -- receive side: framing on the device -------------------------------------------------
     @staticmethod
     def _scan_buffers(count, max_frames, device):
@@ -452,6 +474,25 @@ class Engine:
                                  state_slot: torch.Tensor, slot_bound: int, **kw):
         self._frames_at(lib.fpnn_aes_stream_decrypt_frames_at, "stream_decrypt_frames_at", inp, out, count, keys,
                         iv_state, pos_state, first_frame, nstreams, state_slot, slot_bound, kw)
+
+
+    # One frame per stream by key-table slot: segment i is the pending frame of the connection
+    # in slot state_slot[i] (fpnn_aes_stream_encrypt_at / _decrypt_at); encrypt reaches K2 / K2c /
+    # K2h as stream_encrypt does.
+    def _one_frame_at(self, fn, what, inp, out, count, keys, iv_state, pos_state, state_slot, slot_bound, kw):
+        d = self._desc(inp, out, count, keys, **kw)
+        check(fn(self._h, C.byref(d), self._state_slot(state_slot, count), slot_bound, _ptr(iv_state),
+                 _ptr(pos_state)), what)
+
+    def stream_encrypt_at(self, inp, out, count, keys: "KeySet", iv_state: torch.Tensor, pos_state: torch.Tensor,
+                          state_slot: torch.Tensor, slot_bound: int, **kw):
+        self._one_frame_at(lib.fpnn_aes_stream_encrypt_at, "stream_encrypt_at", inp, out, count, keys, iv_state,
+                           pos_state, state_slot, slot_bound, kw)
+
+    def stream_decrypt_at(self, inp, out, count, keys: "KeySet", iv_state: torch.Tensor, pos_state: torch.Tensor,
+                          state_slot: torch.Tensor, slot_bound: int, **kw):
+        self._one_frame_at(lib.fpnn_aes_stream_decrypt_at, "stream_decrypt_at", inp, out, count, keys, iv_state,
+                           pos_state, state_slot, slot_bound, kw)
 
 
 def host_register(buf: np.ndarray):

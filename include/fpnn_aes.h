@@ -254,6 +254,8 @@ int fpnn_aes_stream_decrypt_frames(fpnn_aes_engine *e, const fpnn_aes_batch *b, 
  *   fpnn_ecdh_accept / fpnn_aes_keyset_set_keys     key and IV into slot s
  *   fpnn_aes_stream_open  x 2 (send pair, recv pair) state of s = (IV of s, 0)
  *   fpnn_aes_stream_*_frames_at / _recv_at           per IO cycle, the active slots only
+ *   fpnn_aes_stream_encrypt_at / _decrypt_at         the same with one frame per slot
+ *   fpnn_aes_stream_host_at                          the same from host socket buffers
  *   fpnn_aes_keyset_clear + fpnn_aes_stream_close x 2   key and state of s are zero
  *
  * fpnn_aes_stream_open: iv_state[16*s_i .. +16] = the IV slot s_i holds, pos_state[s_i] = 0
@@ -294,6 +296,36 @@ int fpnn_aes_stream_encrypt_frames_at(fpnn_aes_engine *e, const fpnn_aes_batch *
 int fpnn_aes_stream_decrypt_frames_at(fpnn_aes_engine *e, const fpnn_aes_batch *b, const uint32_t *first_frame,
                                       uint32_t nstreams, const uint32_t *state_slot, uint32_t slot_bound,
                                       uint8_t *iv_state, uint32_t *pos_state);
+
+/* The common IO cycle by slot: ONE frame per stream.  Segment i of b is the one pending frame of
+ * the connection in slot state_slot[i] (state_slot: DEVICE, b->count entries, 4-byte aligned):
+ * its key is slot state_slot[i] of b->keys, its state entry state_slot[i] of the state arrays
+ * (DEVICE, slot_bound entries, iv_state 16-byte aligned), updated in place.  Results and final
+ * state equal fpnn_aes_stream_encrypt / _decrypt on state gathered from those entries with
+ * key_slot = state_slot -- without the gather and the scatter.
+ * Encrypt takes fpnn_aes_stream_encrypt's dispatch unchanged -- one chain per lane (K2), one
+ * per lane quad (K2c), or, for ragged batches with more chains than the chip has quads, the
+ * length-ordered quad and lane queues (K2h) that balance heavy-tailed frame lengths, which the
+ * *_frames_at walk in stream order does not; b->max_len applies as it does there -- and runs
+ * the kernel in its slot-addressed form.  Decrypt is fpnn_aes_stream_decrypt_frames_at with one
+ * frame per stream (what fpnn_aes_stream_recv_at runs before its scan); the dense whole-stream
+ * decrypt kernels of fpnn_aes_stream_decrypt are not reachable by slot.
+ * FPNN_AES_ERR_ARG: b->key_slot not NULL; with b->count != 0, state_slot NULL or not 4-byte
+ * aligned, iv_state / pos_state NULL or misaligned; slot_bound above
+ * fpnn_aes_keyset_capacity(b->keys); FPNN_AES_F_WIRE_PREFIX set.  b->count == 0 queues nothing.
+ * Queued on the engine's stream; after fpnn_aes_engine_reserve(max_segments, max_blocks) a call
+ * within those bounds allocates nothing (it may be captured in a graph).  Entries of the state
+ * arrays the call does not name keep every bit; naming one slot twice in one call is the
+ * caller's error.  A segment with state_slot[i] >= slot_bound has its state neither read nor
+ * written; encrypt writes no byte of it, decrypt leaves the output bytes of that segment
+ * unspecified and touches no other byte; the other segments are exact, and the next
+ * fpnn_aes_engine_sync returns FPNN_AES_ERR_DEVICE once. */
+int fpnn_aes_stream_encrypt_at(fpnn_aes_engine *e, const fpnn_aes_batch *b,
+        const uint32_t *state_slot, uint32_t slot_bound,   /* dev, b->count entries */
+        uint8_t *iv_state, uint32_t *pos_state);           /* dev, slot_bound entries */
+int fpnn_aes_stream_decrypt_at(fpnn_aes_engine *e, const fpnn_aes_batch *b,
+        const uint32_t *state_slot, uint32_t slot_bound,
+        uint8_t *iv_state, uint32_t *pos_state);
 
 /* ---- single call from host memory (the per-frame drop-in) --------------------------- */
 /* Exactly rijndael_cfb_encrypt(ctx, encrypt, in, out, len, ivec, p_num)
@@ -345,6 +377,24 @@ int fpnn_aes_package_host(fpnn_aes_engine *e, int encrypt, const fpnn_aes_host_f
  * that many successive calls.  Synchronous. */
 int fpnn_aes_stream_host(fpnn_aes_engine *e, int encrypt, const fpnn_aes_host_frame *frames, uint32_t n,
                          const fpnn_aes_keyset *keys, uint8_t *iv_state, uint32_t *pos_state);
+
+/* fpnn_aes_stream_host for connections that live in a key table on the device: frames[i].key_slot
+ * names the table slot, for the key (slot key_slot of `keys`) AND for the state, which stays
+ * where fpnn_aes_stream_open wrote it: iv_state / pos_state are DEVICE arrays of slot_bound
+ * entries (iv_state 16-byte aligned), read and updated by the kernels in place -- neither the
+ * IV nor the state of such a connection is ever in host memory.  src / dst are host pointers
+ * as above; frames in registered memory (fpnn_aes_host_register) take the host-mapped path,
+ * others the staged one.  A slot may appear many times: its frames are processed in array
+ * order, exactly as that many successive StreamEncryptor calls; a slot whose frames are all
+ * empty keeps its state bit for bit, as do the slots the call does not name.  Synchronous, and
+ * ordered behind work already queued on the engine's stream (an fpnn_aes_stream_open queued
+ * just before it is seen).  The host knows every slot: a frame with key_slot >= slot_bound, or
+ * slot_bound > fpnn_aes_keyset_capacity(keys), returns FPNN_AES_ERR_ARG before anything is
+ * queued or touched; so do keys of another device and NULL or misaligned state arrays.  There
+ * is no _multi form: a table lives on one device. */
+int fpnn_aes_stream_host_at(fpnn_aes_engine *e, int encrypt, const fpnn_aes_host_frame *frames, uint32_t n,
+        const fpnn_aes_keyset *keys, uint32_t slot_bound,
+        uint8_t *iv_state /*dev*/, uint32_t *pos_state /*dev*/);
 
 /* One host-frame batch over several engines -- e.g. one per GPU of the node, each
  * with its own copy of the key set (keys[k] created on engines[k], same count and key

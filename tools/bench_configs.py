@@ -11,6 +11,9 @@ for DESIGN.md -- bench.py's single JSON line covers C2 only.
   U1  1M x 1472 B UDP datagrams over 16384 connections, AES-128
   R1  the receive path: 16384 connections x 64 wire frames, fpnn_aes_package_recv (8f row 3)
   S1  stream-mode host frames, 16384 streams x 64 x 1 KiB: staged vs registered (mapped) arenas
+  C4A one frame per stream by key-table slot, C4's length law over 2^18 streams, AES-256 per-slot keys:
+      fpnn_aes_stream_encrypt_at (K2h) against fpnn_aes_stream_encrypt_frames_at (K2f)   (on request)
+  S1A S1 through fpnn_aes_stream_host_at (state in device arrays by table slot)          (on request)
 """
 import argparse
 import json
@@ -360,6 +363,59 @@ def main():
         del a, b, r
         print(json.dumps({"C4": out["C4"]}), flush=True)
 
+    if "C4A" in todo:
+        # One IO cycle of a stream-mode server that keeps its connections in the live key
+        # table: ONE frame per stream, C4's length law (64 r bytes, r ~ Zipf 1.1), 2^18 streams,
+        # AES-256 with a key per slot, the streams' slots a permutation of the table.  The
+        # one-frame call (fpnn_aes_stream_encrypt_at: K2h's length-ordered queues, slot form)
+        # against the many-frames call with an identity first_frame (K2f: streams in index
+        # order).  The two calls alternate, three timed() medians each.
+        import statistics
+        c = dict(W.C4, packets=1 << 18)
+        n = c["packets"]
+        sizes = W.zipf_sizes(c)[:n]
+        assert len(sizes) == n
+        offs = np.concatenate([[0], np.cumsum(sizes[:-1].astype(np.int64))]).astype(np.int64)
+        total = int(offs[-1] + sizes[-1])
+        keys, ivs = W.many_keys(c)
+        ks = fpnn_amd.KeySet(eng, keys.tobytes(), c["keylen"], ivs.tobytes())
+        a = torch.empty(total, dtype=torch.uint8, device="cuda")
+        eng.fill_synthetic(a, c["payload_seed"])
+        b, r = torch.empty_like(a), torch.empty_like(a)
+        slots = torch.from_numpy(np.random.default_rng(c["size_seed"]).permutation(n).astype(np.int32)).cuda()
+        first = torch.arange(n + 1, dtype=torch.int32, device="cuda")
+        iv0 = torch.from_numpy(ivs.copy()).cuda()
+        st_iv, st_pos = iv0.clone(), torch.zeros(n, dtype=torch.int32, device="cuda")
+        kw = dict(in_off=torch.from_numpy(offs).cuda(), lens=torch.from_numpy(sizes.astype(np.int32)).cuda())
+        eng.reserve(n, total // 16 + n)
+
+        def one_frame(dst):
+            eng.stream_encrypt_at(a, dst, n, ks, st_iv, st_pos, slots, n, **kw)
+
+        def many_frames(dst):
+            eng.stream_encrypt_frames_at(a, dst, n, ks, st_iv, st_pos, first, n, slots, n, **kw)
+
+        one_frame(b)
+        at_kernel = eng.last_kernel(E)
+        iv1 = st_iv.clone()
+        st_iv.copy_(iv0)
+        st_pos.zero_()
+        many_frames(r)
+        torch.cuda.synchronize()
+        assert torch.equal(b, r) and torch.equal(iv1, st_iv), "C4A: the two calls differ"
+        runs = {"encrypt_at": [], "encrypt_frames_at": []}
+        for _ in range(3):
+            for tag, fn in (("encrypt_at", lambda: one_frame(b)), ("encrypt_frames_at", lambda: many_frames(r))):
+                w, k, _ = timed(eng, E, fn, args.reps)
+                runs[tag].append((gib(total, k), gib(total, w)))
+        out["C4A"] = {"streams": n, "bytes": total, "encrypt_at_kernel": at_kernel}
+        for tag, v in runs.items():
+            for j, what in enumerate(("kernel", "wall")):
+                x = sorted(t[j] for t in v)
+                out["C4A"][f"{tag}_{what}_GiBs_min_median_max"] = [x[0], statistics.median(x), x[-1]]
+        del a, b, r
+        print(json.dumps({"C4A": out["C4A"]}), flush=True)
+
     if "C3" in todo:
         c = W.C3
         S, L = c["streams"], c["length"]
@@ -583,6 +639,56 @@ def main():
                               "GPU gathers/scatters over PCIe; mapped encrypt output checked equal to the staged one")
         del src, dst
         print(json.dumps({"S1": out["S1"]}), flush=True)
+    if "S1A" in todo:
+        # S1 through fpnn_aes_stream_host_at: the same frames, the streams' (iv, pos) in device
+        # arrays indexed by key-table slot (no 20 B per stream up and down per call)
+        import statistics
+        NS, F, L = 16384, 64, 1024
+        P = NS * F
+        rng = np.random.default_rng(5)
+        keys = rng.integers(0, 256, NS * 16, dtype=np.uint8)
+        ks = fpnn_amd.KeySet(eng, keys.tobytes(), 16, bytes(16 * NS))
+
+        def page_aligned(nbytes):
+            raw = np.empty(nbytes + 4096, dtype=np.uint8)
+            return raw[(-raw.ctypes.data) % 4096:][:nbytes]
+        src, dst = page_aligned(P * L), page_aligned(P * L)
+        src[:] = rng.integers(0, 256, P * L, dtype=np.uint8)
+        perm = rng.permutation(P).astype(np.uint64)
+        fr = np.zeros(P, dtype=fpnn_amd.engine.HOST_FRAME_DTYPE)
+        fr["src"] = src.ctypes.data + perm * L
+        fr["dst"] = dst.ctypes.data + perm[::-1] * L
+        fr["len"] = L
+        fr["key_slot"] = np.arange(P) % NS
+        eng.stream_host_array(True, fr, ks, np.zeros(16 * NS, np.uint8), np.zeros(NS, np.uint32))
+        ref_enc = dst.copy()
+        res = {}
+        for mode in ("staged", "mapped"):
+            if mode == "mapped":
+                fpnn_amd.host_register(src)
+                fpnn_amd.host_register(dst)
+            for enc in (True, False):
+                times = []
+                for _ in range(1 + args.reps):
+                    iv = torch.zeros(16 * NS, dtype=torch.uint8, device="cuda")
+                    pos = torch.zeros(NS, dtype=torch.int32, device="cuda")
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    eng.stream_host_at(enc, fr, ks, NS, iv, pos)
+                    times.append(time.perf_counter() - t0)
+                x = sorted(gib(P * L, t) for t in times[1:])
+                res[f"{mode}_{'encrypt' if enc else 'decrypt'}_GiBs_min_median_max"] = [x[0], statistics.median(x), x[-1]]
+                res[f"{mode}_path"] = eng.last_kernel(fpnn_amd.K_HOST)
+                if enc:
+                    assert np.array_equal(dst, ref_enc), f"{mode} stream_host_at differs from stream_host"
+            if mode == "mapped":
+                fpnn_amd.host_unregister(src)
+                fpnn_amd.host_unregister(dst)
+        out["S1A"] = dict(res, frames=P, streams=NS, frame_bytes=L,
+                          note="S1's frames through fpnn_aes_stream_host_at: state in device arrays by table slot; "
+                               "encrypt output checked equal to fpnn_aes_stream_host's")
+        del src, dst
+        print(json.dumps({"S1A": out["S1A"]}), flush=True)
     if "SB" in todo:
         # Small receive batches (one IO cycle of a server): 256 package frames of 64 .. 2047
         # bytes (AES-256, one key) per call, 2 000 calls back to back -- the shape where a
