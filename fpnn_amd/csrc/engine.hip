@@ -1,10 +1,11 @@
 // engine.hip -- implementation of the C-ABI declared in include/fpnn_aes.h.
 //
-// Host-side responsibilities only: argument checking, key-set management, scratch
-// sizing, choosing the kernel variant (uniform vs general layout, uniform vs
-// per-packet keys, package vs stream, in-place) and queuing it on the engine's
-// HIP stream.  There is no CPU cipher in this library: every byte of payload is
-// transformed by the HIP kernels in k_encrypt.hip / k_decrypt.hip.
+// Host-side responsibilities only: argument checking, key-set management, growing the
+// scratch and queuing the kernels on the engine's HIP stream.  Which kernel a batch runs on
+// (uniform vs general layout, uniform vs per-packet keys, package vs stream, in-place) is
+// dispatch_plan.hpp's decision, how much scratch it needs scratch_plan.hpp's.  There is no
+// CPU cipher in this library: every byte of payload is transformed by the HIP kernels in
+// k_encrypt.hip / k_decrypt.hip.
 // (The calls that take many frames from host memory are in host_frames.hip.)
 #include <sys/random.h>
 
@@ -28,15 +29,16 @@ const uint8_t *isbox_of(const fpnn_aes_engine *e) { return e->d_tables + 2304; }
 // capacity of its own until it grows)
 uint32_t table_slots(const fpnn_aes_keyset *ks) { return std::max(ks->capacity, ks->count); }
 
-// the smallest power-of-two workgroup (at least one wave) that still spreads `lanes` over
-// every CU, and its grid: at most one workgroup per CU (further work grid-strides)
-struct Spread { int threads, grid; };
-Spread spread_over_cus(const fpnn_aes_engine *e, uint64_t lanes) {
-    int threads = 64;
-    while (threads < kThreads && (uint64_t)threads * e->num_cus < lanes) threads *= 2;
-    const uint64_t want = (lanes + threads - 1) / threads;
-    return {threads, (int)(want < (uint64_t)e->num_cus ? (want ? want : 1) : (uint64_t)e->num_cus)};
+// what dispatch_plan.hpp reads of the engine and of a batch
+DispatchShape dispatch_shape(const fpnn_aes_engine *e) {
+    return {scratch_shape(e), kThreads, kFrameMaxBytes, e->variant.hyb_long, e->variant.hyb_quad_waves,
+            e->variant.hyb_force, length_bucket_of};
 }
+BatchShape batch_shape(const fpnn_aes_batch *b) {
+    return {b->count, b->stride, b->uniform_len, b->max_len, b->flags, b->in_off != nullptr, b->out_off != nullptr,
+            b->len != nullptr, b->key_slot != nullptr, b->keys->count, b->in == b->out};
+}
+static_assert(F_WIRE_PREFIX == FPNN_AES_F_WIRE_PREFIX, "the plan reads the public flag");
 
 void free_deferred(fpnn_aes_engine *e) {  // the engine's stream is idle
     for (void *p : e->deferred) (void)hipFree(p);
@@ -104,18 +106,20 @@ int timing_end(fpnn_aes_engine *e, EventPair *pair, int which) {
     return FPNN_AES_OK;
 }
 
-// ceil(2^64 / d) for 1 <= d < 2^32
-uint64_t magic_for(uint32_t d) {
-    if (d == 1) return 0;  // unused: fast path divides by 1 via umulhi(g, 0) -> wrong, handled below
-    const unsigned __int128 one = (unsigned __int128)1 << 64;
-    return (uint64_t)((one + d - 1) / d);
-}
-
 int check_batch(const fpnn_aes_engine *e, const fpnn_aes_batch *b) {
     if (!e || !b || !b->keys) return FPNN_AES_ERR_ARG;
     if (b->count && (!b->in || !b->out)) return FPNN_AES_ERR_ARG;
     if (b->keys->device != e->device) return FPNN_AES_ERR_ARG;
     if (b->keys->count == 0) return FPNN_AES_ERR_ARG;
+    return FPNN_AES_OK;
+}
+
+// The device state arrays of a stream call with n streams: there and 16-byte aligned when
+// n > 0.  pos4: pos_state on a 4-byte grid as well -- the *_frames calls ask that of a call
+// with streams, the one-frame _at encrypt of every call, the plain stream calls never.
+int check_stream_state(uint64_t n, const uint8_t *iv_state, const uint32_t *pos_state, bool pos4) {
+    if (n && (!iv_state || !pos_state || ((uintptr_t)iv_state & 15))) return FPNN_AES_ERR_ARG;
+    if (pos4 && ((uintptr_t)pos_state & 3)) return FPNN_AES_ERR_ARG;
     return FPNN_AES_OK;
 }
 
@@ -148,10 +152,6 @@ void devkey_from_schedule(DevKey *hk, const fpnn_aes_schedule *ctx, const uint8_
     hk->nrounds = (uint32_t)ctx->nrounds;
     hk->keylen = (uint32_t)(ctx->nrounds - 6) * 4;
     if (iv) memcpy(hk->iv, iv, 16);
-}
-
-bool is_uniform_layout(const fpnn_aes_batch *b) {
-    return !b->in_off && !b->out_off && !b->len && !b->key_slot;
 }
 
 #ifdef FPNN_AES_BOUNDS
@@ -307,19 +307,23 @@ int check_slot_addr(const fpnn_aes_batch *b, uint64_t nstreams, const SlotAddr *
     return FPNN_AES_OK;
 }
 
-// at (fpnn_aes_stream_encrypt_at, stream mode): the dispatch below is the same, and the kernel it
-// picks runs in its slot form (KEY_SLOT, k_stream_at.hip).
+// at (fpnn_aes_stream_encrypt_at, stream mode): the route is the same, and its kernel runs in its
+// slot form (KEY_SLOT, k_stream_at.hip).
 int run_encrypt_calls(fpnn_aes_engine *e, const fpnn_aes_batch *b, uint8_t *iv_state, uint32_t *pos_state, bool stream,
                       const SlotAddr *at = nullptr) {
     int rc = check_batch(e, b);
     if (rc) return rc;
-    if (stream && b->count && (!iv_state || !pos_state || ((uintptr_t)iv_state & 15))) return FPNN_AES_ERR_ARG;
-    if (at && ((rc = check_slot_addr(b, b->count, at)) || ((uintptr_t)pos_state & 3))) return FPNN_AES_ERR_ARG;
+    if (stream && (rc = check_stream_state(b->count, iv_state, pos_state, at != nullptr))) return rc;
+    if (at && (rc = check_slot_addr(b, b->count, at))) return rc;
     if (!stream && (b->flags & FPNN_AES_F_WIRE_PREFIX) && (b->out_off == nullptr && b->in == b->out))
         return FPNN_AES_ERR_ARG;  // the 4-byte prefix needs a distinct output layout
     if (!b->count) return FPNN_AES_OK;
     DeviceGuard g(e->device);
     const BatchScope batch_scope(e);  // (an early return clears the pending flag)
+    const EncryptRoute r = encrypt_route(dispatch_shape(e), batch_shape(b), {stream, at != nullptr});
+    // (everything that can fail is done before the length order is queued: its block is
+    // left dirty until its last reader runs)
+    if ((rc = scratch_ensure(e, r.need))) return rc;
     KBatch k = make_kbatch(e, b, iv_state, pos_state);
     if (at) {
         k.state_slot = at->state_slot;
@@ -331,89 +335,43 @@ int run_encrypt_calls(fpnn_aes_engine *e, const fpnn_aes_batch *b, uint8_t *iv_s
     } else if ((rc = audit_begin(e, b, iv_state, pos_state, k))) {
         return rc;
     }
-    const Layout layout = is_uniform_layout(b) ? LAYOUT_UNIFORM : LAYOUT_GENERAL;
-    const KeyMode km = at ? KEY_SLOT : (b->key_slot && b->keys->count > 1) ? KEY_LANE : KEY_UNIFORM;
-    // Few chains (fewer than the lanes of a full chip) or ragged lengths: one quad per
-    // chain (K2c); otherwise one lane per chain with 8-block chunks (K2).
-    const uint64_t full_chip = (uint64_t)e->num_cus * kThreads;
-
-    // Ragged package batches of many short frames (the caller's max_len bound): one lane
-    // per chain in grid-stride order (K2) -- Q1, 2 M x 145-B quests of 16 384 keyed
-    // connections: 705 against K2h's 343 GiB/s (its work-queue atomics and length-order
-    // indirection per chain; profiles/r05/ab_k2_short, ab_k2_align), from one chain per
-    // GPU lane on (Q1h, 2 per lane: K2 767-770 against K2h 182-184 GiB/s,
-    // profiles/r05/ab_k2_short_min).  Without a bound K2h, which also balances
-    // Zipf-like lengths (C4 on K2: 88 GiB/s).
-    const bool k2_ragged = b->len && !stream && b->max_len && b->max_len <= 2048 && b->count >= full_chip;
-    if ((b->count < full_chip || b->len != nullptr) && !k2_ragged) {
-        const uint64_t lanes = 4 * b->count;
-        const Spread sp = spread_over_cus(e, lanes);
-        // ragged with more chains than quads: K2h (short chains one per lane, the longest
-        // on quads, both from work queues); with fewer every quad holds at most one chain
-        // and K2c's grid stride is cheaper
-        const bool hybrid = b->len && b->count > 1 && (lanes > full_chip || e->variant.hyb_force);
-        uint32_t *block = nullptr;  // the length-order block (ragged batches)
-        if (b->len && b->count > 1) {  // ragged: visit the longest chains first, similar lengths per wave
-            // (everything that can fail is done before the length order is queued: its block is
-            // left dirty until its last reader runs)
-            if ((rc = scratch_ensure(e, need_encrypt_ragged(scratch_shape(e), b->count, hybrid)))) return rc;
-            // bucket sizes read pos_state (the encrypt kernel reads it later); the slot form
-            // orders by length alone (the position is the slot's: kernels.hpp)
-            const bool order_pos = stream && !at;
-            if (order_pos) k.pos_snap = pos_state;
-            block = e->buckets.p;
-            if (e->variant.poison_order > 0) {  // (tests) bucket counts left over as if by a lost call
-                e->variant.poison_order--;
-                HIP_TRY(hipMemsetAsync(block, 0x01, kWireFlagWord / 2 * sizeof(uint32_t), e->stream));
-            }
-            HIP_TRY(launch_length_order(k, order_pos, e->perm.p, block, !hybrid, e->d_fault, e->stream));
-            k.perm = e->perm.p;
+    uint32_t *block = nullptr;  // the length-order block (ragged batches)
+    if (r.order) {
+        if (r.order_pos) k.pos_snap = pos_state;  // bucket sizes read it (the encrypt kernel reads it later)
+        block = e->buckets.p;
+        if (e->variant.poison_order > 0) {  // (tests) bucket counts left over as if by a lost call
+            e->variant.poison_order--;
+            HIP_TRY(hipMemsetAsync(block, 0x01, kWireFlagWord / 2 * sizeof(uint32_t), e->stream));
         }
-        EventPair *ev;
-        if ((rc = timing_begin(e, FPNN_AES_K_ENCRYPT, &ev))) {
-            if (block) (void)hipMemsetAsync(block, 0, kLengthOrderWords * sizeof(uint32_t), e->stream);
-            return rc;
-        }
-        if (hybrid) {  // K2h: one lane per chain, quads for the longest; one workgroup per CU
-            k.flags |= F_ALIGN_CHUNKS;
-            HybridArgs h;
-            h.ctr = block + kTicketWords;
-            h.buckets = block;
-            h.long_bucket = length_bucket_of((uint64_t)e->variant.hyb_long);
-            h.quad_waves = (uint32_t)e->variant.hyb_quad_waves;
-            h.sink = e->sink.p;
-            if (b->flags & FPNN_AES_F_WIRE_PREFIX) {
-                // wire frames (htole32(len) || C): every chain on quads (k_hybrid.hip's
-                // launcher takes the quads-only kernel for them)
-                h.long_bucket = 127;
-                h.quad_waves = 16;
-            }
-            if (at) HIP_TRY(launch_encrypt_hybrid_at(k, h, b->keys->nrounds, e->num_cus, e->stream));
-            else HIP_TRY(launch_encrypt_hybrid(k, h, b->keys->nrounds, km, stream, e->num_cus, e->stream));
-        } else if (at) {
-            HIP_TRY(launch_encrypt_coop_at(k, b->keys->nrounds, layout, sp.grid, sp.threads, e->stream));
-        } else {
-            HIP_TRY(launch_encrypt_coop(k, b->keys->nrounds, layout, km, stream, sp.grid, sp.threads, e->stream));
-        }
-        return timing_end(e, ev, FPNN_AES_K_ENCRYPT);
+        HIP_TRY(launch_length_order(k, r.order_pos, e->perm.p, block, r.order_zeroes, e->d_fault, e->stream));
+        k.perm = e->perm.p;
     }
-    // One lane per chain.  Workgroup size: the smallest power of two (>= one wave) that
-    // still spreads the chains over every CU -- with few chains (C3: 4096 streams) a
-    // 1024-thread workgroup would pack them onto a handful of CUs whose LDS they then
-    // saturate, while the rest of the chip idles.
-    const Spread sp = spread_over_cus(e, b->count);
-    // (not for ragged batches by default, Variant::k2_align_ragged: a few 16-B aligned
-    // frames per wave made the whole wave run their singles)
-    if (!b->len) k.flags |= F_ALIGN_CHUNKS;
+    k.flags |= r.flags;  // (the cipher kernel's alone: the length order has read k without them)
     EventPair *ev;
-    if ((rc = timing_begin(e, FPNN_AES_K_ENCRYPT, &ev))) return rc;
-    if (k2_ragged && b->max_len <= kFrameMaxBytes)  // FPNN's quests: whole frames at once (K2s-DB)
-        HIP_TRY(launch_encrypt_frames(k, b->keys->nrounds, km, (b->flags & FPNN_AES_F_WIRE_PREFIX) != 0,
-                                      e->num_cus, e->stream));
-    else if (at)
-        HIP_TRY(launch_encrypt_chains_at(k, b->keys->nrounds, layout, sp.grid, sp.threads, e->stream));
-    else
-        HIP_TRY(launch_encrypt_chains(k, b->keys->nrounds, layout, km, stream, sp.grid, sp.threads, e->stream));
+    if ((rc = timing_begin(e, FPNN_AES_K_ENCRYPT, &ev))) {
+        if (block) (void)hipMemsetAsync(block, 0, kLengthOrderWords * sizeof(uint32_t), e->stream);
+        return rc;
+    }
+    const int nr = b->keys->nrounds;
+    switch (r.family) {
+    case ENC_HYBRID: {
+        const HybridArgs h{block + kTicketWords, block, r.long_bucket, r.quad_waves, e->sink.p};
+        if (at) HIP_TRY(launch_encrypt_hybrid_at(k, h, nr, r.grid, e->stream));
+        else HIP_TRY(launch_encrypt_hybrid(k, h, nr, r.km, stream, r.grid, e->stream));
+        break;
+    }
+    case ENC_COOP:
+        if (at) HIP_TRY(launch_encrypt_coop_at(k, nr, r.layout, r.grid, r.threads, e->stream));
+        else HIP_TRY(launch_encrypt_coop(k, nr, r.layout, r.km, stream, r.grid, r.threads, e->stream));
+        break;
+    case ENC_FRAMES:
+        HIP_TRY(launch_encrypt_frames(k, nr, r.km, r.wire, r.grid, e->stream));
+        break;
+    case ENC_CHAINS:
+        if (at) HIP_TRY(launch_encrypt_chains_at(k, nr, r.layout, r.grid, r.threads, e->stream));
+        else HIP_TRY(launch_encrypt_chains(k, nr, r.layout, r.km, stream, r.grid, r.threads, e->stream));
+        break;
+    }
     return timing_end(e, ev, FPNN_AES_K_ENCRYPT);
 }
 
@@ -431,13 +389,11 @@ struct SnapCopy {  // what the single-workgroup block map's state copy reads and
 
 // K1r on the batch k describes: block-map scan, per-wave plan and decrypt all on the device;
 // the host never learns the block total, so nothing here waits for the GPU.  What can fail
-// comes first: the scratch (`need`) is grown before anything is queued.  before(small_map,
-// snap) then queues what the caller runs ahead of the block map (state snapshot or pre-pass),
-// points k at it and says what a small (single-workgroup) block map copies as its snapshot.
+// has come first: the caller has grown the scratch of its route.  before(small_map, snap)
+// queues what the caller runs ahead of the block map (state snapshot or pre-pass), points k
+// at it and says what a small (single-workgroup) block map copies as its snapshot.
 template <class Before>
-int decrypt_ragged(fpnn_aes_engine *e, const fpnn_aes_batch *b, KBatch &k, bool stream, KeyMode km,
-                   const ScratchNeed &need, Before before) {
-    if (int rc = scratch_ensure(e, need)) return rc;
+int decrypt_ragged(fpnn_aes_engine *e, const fpnn_aes_batch *b, KBatch &k, bool stream, KeyMode km, Before before) {
     const bool small_map = b->count <= block_map_small_max();
     SnapCopy snap;
     if (int rc = before(small_map, snap)) return rc;
@@ -469,78 +425,45 @@ int decrypt_ragged(fpnn_aes_engine *e, const fpnn_aes_batch *b, KBatch &k, bool 
 int run_decrypt(fpnn_aes_engine *e, const fpnn_aes_batch *b, uint8_t *iv_state, uint32_t *pos_state, bool stream) {
     int rc = check_batch(e, b);
     if (rc) return rc;
-    if (stream && b->count && (!iv_state || !pos_state || ((uintptr_t)iv_state & 15))) return FPNN_AES_ERR_ARG;
+    if (stream && (rc = check_stream_state(b->count, iv_state, pos_state, false))) return rc;
     if (b->flags & FPNN_AES_F_WIRE_PREFIX) return FPNN_AES_ERR_ARG;
     if (!b->count) return FPNN_AES_OK;
     DeviceGuard g(e->device);
     const BatchScope batch_scope(e);  // (an early return clears the pending flag)
+    const DecryptRoute r = decrypt_route(dispatch_shape(e), batch_shape(b), {stream, false});
+    if ((rc = scratch_ensure(e, r.need))) return rc;
     KBatch k = make_kbatch(e, b, iv_state, pos_state);
-    // In place whenever the buffers coincide (K1 / K1d: a wave may overwrite the
-    // ciphertext block another wave's lane 0 still needs, so chunk boundaries are saved
-    // first; K1r saves its waves' boundaries in its plan in any case).
-    const bool inplace = b->in == b->out;
-    const KeyMode km = (b->key_slot && b->keys->count > 1) ? KEY_LANE : KEY_UNIFORM;
-    // Uniform layout: every segment has the same block count, known on the host.
-    // (Stream mode only when there is a single segment, whose position the caller
-    // supplies through the host path; otherwise positions differ per stream.)
-    Layout layout = LAYOUT_GENERAL;
-    auto uniform_blocks = [&](uint64_t nb, Layout l) {  // nb blocks per segment, fewer than 2^32 in all
-        layout = l;
-        k.total_blocks = nb * b->count;
-        k.nb_uniform = (uint32_t)nb;
-        k.magic = magic_for((uint32_t)nb);
-    };
-    if (is_uniform_layout(b) && !stream) {
-        const uint64_t nb = ((uint64_t)b->uniform_len + 15) >> 4;
-        if (nb > 1 && nb * b->count < (1ull << 32))
-            uniform_blocks(nb, (b->uniform_len & 15) == 0 ? LAYOUT_FULL : LAYOUT_UNIFORM);
-    } else if (!stream && km == KEY_LANE && !b->in_off && !b->out_off && !b->len &&
-               b->uniform_len >= 32 && b->uniform_len % 16 == 0 && b->stride == b->uniform_len) {
-        // dense whole-block packets, one key slot each: K1d with a wave-uniform key per
-        // step when packets are whole 64-block chunks (C5), K1k with per-lane keys
-        // otherwise (U1)
-        const uint64_t nb = b->uniform_len >> 4;
-        if (nb * b->count < (1ull << 32)) uniform_blocks(nb, LAYOUT_FULL);
-    }
-    // Ragged package batches of FPNN's quests (the caller's max_len bound, at least one frame
-    // per GPU lane): one lane per frame, its blocks decrypted as independent AES passes from
-    // registers (D2s).  K1r's 64-block chunks span ~7 frames and key slots there.
-    if (layout == LAYOUT_GENERAL && !stream && b->len && b->max_len && b->max_len <= kFrameMaxBytes &&
-        b->count >= (uint64_t)e->num_cus * kThreads) {
-        EventPair *ev = nullptr;
-        if ((rc = timing_begin(e, FPNN_AES_K_DECRYPT, &ev))) return rc;
-        HIP_TRY(launch_decrypt_frames(k, b->keys->nrounds, km, e->num_cus, e->stream));
-        return timing_end(e, ev, FPNN_AES_K_DECRYPT);
-    }
-    if (layout == LAYOUT_GENERAL) {  // K1r; stream batches (which always come here) snapshot their state first
-        const uint64_t n = b->count;
-        return decrypt_ragged(e, b, k, stream, km, need_decrypt_ragged(scratch_shape(e), n, stream, b->in_off, b->len),
-                              [&](bool small_map, SnapCopy &snap) {
-                                  if (!stream) return (int)FPNN_AES_OK;
-                                  if (!small_map) {  // (the small block map copies the snapshot itself)
-                                      HIP_TRY(hipMemcpyAsync(e->snap_iv.p, iv_state, 16ull * n, hipMemcpyDeviceToDevice,
-                                                             e->stream));
-                                      HIP_TRY(hipMemcpyAsync(e->snap_pos.p, pos_state, 4ull * n, hipMemcpyDeviceToDevice,
-                                                             e->stream));
-                                  }
-                                  k.iv_snap = e->snap_iv.p;  // see KBatch::iv_snap
-                                  k.pos_snap = e->snap_pos.p;
-                                  snap = {iv_state, pos_state, e->snap_iv.p, e->snap_pos.p};
-                                  return (int)FPNN_AES_OK;
-                              });
-    }
     EventPair *ev = nullptr;
-    const uint64_t nchunks = (k.total_blocks + 63) >> 6;
-    if (inplace) {
-        if ((rc = scratch_ensure(e, need_decrypt_dense_inplace(k.total_blocks)))) return rc;
-        HIP_TRY(launch_boundary_save(k, e->boundary.p, nchunks, e->stream));
-        k.boundary = e->boundary.p;
+    switch (r.family) {
+    case DEC_RAGGED:  // stream batches (which always come here) snapshot their state first
+        return decrypt_ragged(e, b, k, stream, r.km, [&](bool small_map, SnapCopy &snap) {
+            if (!stream) return (int)FPNN_AES_OK;
+            const uint64_t n = b->count;
+            if (!small_map) {  // (the small block map copies the snapshot itself)
+                HIP_TRY(hipMemcpyAsync(e->snap_iv.p, iv_state, 16ull * n, hipMemcpyDeviceToDevice, e->stream));
+                HIP_TRY(hipMemcpyAsync(e->snap_pos.p, pos_state, 4ull * n, hipMemcpyDeviceToDevice, e->stream));
+            }
+            k.iv_snap = e->snap_iv.p;  // see KBatch::iv_snap
+            k.pos_snap = e->snap_pos.p;
+            snap = {iv_state, pos_state, e->snap_iv.p, e->snap_pos.p};
+            return (int)FPNN_AES_OK;
+        });
+    case DEC_FRAMES:
+        if ((rc = timing_begin(e, FPNN_AES_K_DECRYPT, &ev))) return rc;
+        HIP_TRY(launch_decrypt_frames(k, b->keys->nrounds, r.km, r.grid, e->stream));
+        break;
+    case DEC_DENSE:
+        k.total_blocks = r.total_blocks;
+        k.nb_uniform = r.nb_uniform;
+        k.magic = r.magic;
+        if (r.boundary_save) {
+            HIP_TRY(launch_boundary_save(k, e->boundary.p, r.nchunks, e->stream));
+            k.boundary = e->boundary.p;
+        }
+        if ((rc = timing_begin(e, FPNN_AES_K_DECRYPT, &ev))) return rc;
+        HIP_TRY(launch_decrypt_blocks(k, b->keys->nrounds, r.layout, r.km, r.boundary_save, r.grid, e->stream));
+        break;
     }
-    const uint64_t want = (nchunks + 63) / 64;  // 16 waves per workgroup x up to 4 chunks per wave step
-    const uint64_t cap = (uint64_t)e->num_cus;
-    const int grid = (int)(want < cap ? (want ? want : 1) : cap);
-    if ((rc = timing_begin(e, FPNN_AES_K_DECRYPT, &ev))) return rc;
-    HIP_TRY(launch_decrypt_blocks(k, b->keys->nrounds, layout, km, inplace, grid, e->stream));
     return timing_end(e, ev, FPNN_AES_K_DECRYPT);
 }
 
@@ -551,10 +474,9 @@ int check_frames(const fpnn_aes_engine *e, const fpnn_aes_batch *b, const uint32
     const int rc = check_batch(e, b);
     if (rc) return rc;
     if (b->flags & FPNN_AES_F_WIRE_PREFIX) return FPNN_AES_ERR_ARG;
+    if (int src = check_stream_state(nstreams, iv_state, pos_state, nstreams != 0)) return src;
     const bool need_first = !(at && at->one_frame);
-    if (nstreams && ((need_first && !first_frame) || !iv_state || !pos_state || ((uintptr_t)iv_state & 15) ||
-                     ((uintptr_t)pos_state & 3) || ((uintptr_t)first_frame & 3)))
-        return FPNN_AES_ERR_ARG;
+    if (nstreams && ((need_first && !first_frame) || ((uintptr_t)first_frame & 3))) return FPNN_AES_ERR_ARG;
     if (at) return check_slot_addr(b, nstreams, at);
     return FPNN_AES_OK;
 }
@@ -580,12 +502,10 @@ int run_encrypt_frames_calls(fpnn_aes_engine *e, const fpnn_aes_batch *b, const 
     KBatch k = make_kbatch(e, b, iv_state, pos_state);
     const FrameTable f = frame_table(e, first_frame, nstreams, at);
     if ((rc = audit_begin(e, b, iv_state, pos_state, k, &f))) return rc;
-    // (an _at call: every stream's key from its slot of the table, whatever the table's size)
-    const KeyMode km = (at || (b->key_slot && b->keys->count > 1)) ? KEY_LANE : KEY_UNIFORM;
-    const Spread sp = spread_over_cus(e, 4ull * nstreams);
+    const FramesRoute r = frames_route(dispatch_shape(e), batch_shape(b), at != nullptr, nstreams, true);
     EventPair *ev;
     if ((rc = timing_begin(e, FPNN_AES_K_ENCRYPT, &ev))) return rc;
-    HIP_TRY(launch_encrypt_stream_frames(k, f, b->keys->nrounds, km, sp.grid, sp.threads, e->stream));
+    HIP_TRY(launch_encrypt_stream_frames(k, f, b->keys->nrounds, r.km, r.grid, r.threads, e->stream));
     return timing_end(e, ev, FPNN_AES_K_ENCRYPT);
 }
 
@@ -600,11 +520,13 @@ int run_decrypt_frames_calls(fpnn_aes_engine *e, const fpnn_aes_batch *b, const 
     if (!nstreams || !b->count) return FPNN_AES_OK;
     DeviceGuard g(e->device);
     const BatchScope batch_scope(e);
+    const FramesRoute r = frames_route(dispatch_shape(e), batch_shape(b), at != nullptr, nstreams, false);
+    if ((rc = scratch_ensure(e, r.need))) return rc;
     KBatch k = make_kbatch(e, b, iv_state, pos_state);
     FrameTable f = frame_table(e, first_frame, nstreams, at);
-    const KeyMode km = (at || (b->key_slot && b->keys->count > 1)) ? KEY_LANE : KEY_UNIFORM;
+    const KeyMode km = r.km;
     rc = decrypt_ragged(
-        e, b, k, true, km, need_decrypt_frames(scratch_shape(e), b->count, at != nullptr, b->in_off, b->len),
+        e, b, k, true, km,
         [&](bool, SnapCopy &snap) {
             if (at) {  // the walk writes every segment's key slot; the pre-pass's second launch and K1r read it
                 f.seg_slot = e->sf_slot.p;
@@ -1283,7 +1205,7 @@ int fpnn_aes_package_recv(fpnn_aes_engine *e, const fpnn_aes_batch *b, uint32_t 
     const uint64_t slots = (uint64_t)b->count * max_frames;
     if (slots > 0xffffffffull) return FPNN_AES_ERR_RANGE;
     DeviceGuard g(e->device);
-    const bool per_key = b->key_slot && b->keys->count > 1;
+    const bool per_key = fpnn_aes::per_key(batch_shape(b));
     if ((rc = e->fr_off.ensure(e, slots))) return rc;
     if (per_key && (rc = e->fr_slot.ensure(e, slots))) return rc;
     KScan s;

@@ -7,11 +7,11 @@
 
 #include "aes_common.hpp"
 #include "audit.hpp"
+#include "dispatch_plan.hpp"
 
 namespace fpnn_aes {
 
-constexpr uint32_t F_WIRE_PREFIX = 0x1u;
-constexpr uint32_t F_ALIGN_CHUNKS = 0x100u;  // internal (engine -> K2): line-align the chunks of each chain
+// (F_WIRE_PREFIX, F_ALIGN_CHUNKS, Layout and KeyMode: dispatch_plan.hpp, which chooses them)
 
 // Kernel-side view of one batch (passed by value as the kernel argument).
 struct KBatch {
@@ -65,17 +65,6 @@ struct KBatch {
     // the address-audit build's extent table (audit.hpp; null in the product build)
     AuditTable *aud;
 };
-
-// UNIFORM: segment i at i*stride, uniform_len bytes, key slot 0.  FULL: the same with
-// uniform_len % 16 == 0 in package mode, so no block is partial (decrypt skips the
-// byte-granular head/tail paths); with KEY_LANE, FULL also means dense (stride ==
-// uniform_len) with key_slot[] holding one slot per packet (K1d keyed when
-// uniform_len % 1024 == 0, else K1k).
-// GENERAL: offset/length/slot arrays (decrypt: K1r, k_ragged.hip).
-enum Layout { LAYOUT_UNIFORM = 0, LAYOUT_GENERAL = 1, LAYOUT_FULL = 2 };
-// KEY_SLOT (stream encrypt only): per-lane keys as KEY_LANE, and the segment's (iv, pos)
-// lives at its key slot -- KBatch::state_slot; launch_encrypt_*_at below.
-enum KeyMode { KEY_UNIFORM = 0, KEY_LANE = 1, KEY_SLOT = 2 };
 
 // Per-engine dispatch settings that tests set (tests/conftest.py) so that small batches
 // reach every session of the shipped kernels.  Round 4 removed the measured-and-rejected
