@@ -516,7 +516,8 @@ def test_dense_layout(engine, oracle, keylen, length, n):
     """Dense whole-block batches (stride == length, length % 16 == 0): the K1d decrypt
     path -- chunk-aligned packets (length % 1 KiB == 0) and packet starts inside a
     chunk, partial last chunk (n = 2501), in place and out of place.  The 64 guard
-    bytes after the batch must survive."""
+    bytes after the batch must survive.  At these sizes every wave takes one step; the
+    prefetch ping-pong and the tail step after it run in tests/test_gpu_full_chip.py."""
     rng = np.random.default_rng(length * 11 + keylen + n)
     inp = rng.integers(0, 256, n * length + 64, dtype=np.uint8)
     key, iv = rng.bytes(keylen), rng.bytes(16)
