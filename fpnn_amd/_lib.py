@@ -75,6 +75,24 @@ class BatchDesc(C.Structure):
     ]
 
 
+class UdpData(C.Structure):
+    """fpnn_aes_udp_data (include/fpnn_aes.h)."""
+
+    _fields_ = [
+        ("data_keys", C.c_void_p),
+        ("nconn", C.c_uint32),
+        ("first_dgram", C.c_void_p),
+        ("conn_slot", C.c_void_p),
+        ("slot_bound", C.c_uint32),
+        ("nsections", C.c_uint32),
+        ("first_section", C.c_void_p),
+        ("sec_off", C.c_void_p),
+        ("sec_len", C.c_void_p),
+        ("iv_state", C.c_void_p),
+        ("pos_state", C.c_void_p),
+    ]
+
+
 _vp = C.c_void_p
 _u8p = C.POINTER(C.c_uint8)
 
@@ -102,6 +120,7 @@ SIGNATURES = {
     "fpnn_aes_copy_async": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
     "fpnn_aes_engine_numa": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "fpnn_aes_engine_reserve": (C.c_int, [_vp, C.c_uint64, C.c_uint64]),
+    "fpnn_aes_engine_scratch_bytes": (C.c_uint64, [_vp]),
     "fpnn_aes_keyset_create": (C.c_int, [_vp, C.c_uint32, C.c_size_t, _vp, _vp, C.c_int, C.POINTER(_vp)]),
     "fpnn_aes_keyset_from_schedules": (C.c_int, [_vp, C.c_uint32, C.POINTER(Schedule), _vp, C.POINTER(_vp)]),
     "fpnn_aes_keyset_destroy": (C.c_int, [_vp]),
@@ -125,6 +144,8 @@ SIGNATURES = {
                                                     _vp]),
     "fpnn_aes_stream_decrypt_frames_at": (C.c_int, [_vp, C.POINTER(BatchDesc), _vp, C.c_uint32, _vp, C.c_uint32, _vp,
                                                     _vp]),
+    "fpnn_aes_udp_encrypt": (C.c_int, [_vp, C.POINTER(BatchDesc), C.POINTER(UdpData)]),
+    "fpnn_aes_udp_decrypt": (C.c_int, [_vp, C.POINTER(BatchDesc), C.POINTER(UdpData)]),
     "fpnn_aes_cfb_host": (C.c_int, [_vp, C.POINTER(Schedule), C.c_int, _vp, _vp, C.c_size_t, _u8p,
                                     C.POINTER(C.c_size_t)]),
     "fpnn_aes_package_host": (C.c_int, [_vp, C.c_int, C.POINTER(HostFrame), C.c_uint32, _vp, C.c_uint32]),

@@ -48,6 +48,10 @@ enum AuditBuf : uint32_t {
     AB_STATE_SLOT,  // slot-addressed stream calls: state_slot[], nstreams entries (the state arrays
                     // then hold slot_bound entries)
     AB_SEG_SLOT,    // their decrypt: the per-segment key slots the walk writes, `count` entries
+    AB_UDP_DATA_KEYS,      // the UDP calls (k_udp.hip): the data table's DevKey slots,
+    AB_UDP_FIRST_SECTION,  // first_section[], count + 1 entries,
+    AB_UDP_SEC_OFF,        // sec_off[] and sec_len[], nsections entries each (first_dgram[] and
+    AB_UDP_SEC_LEN,        // conn_slot[] are checked as AB_FIRST_FRAME and AB_STATE_SLOT)
     kAuditBufs
 };
 

@@ -261,4 +261,72 @@ inline FramesRoute frames_route(const DispatchShape &d, const BatchShape &b, boo
     return r;
 }
 
+// ---- UDP v2 datagrams with data encryption (fpnn_aes_udp_encrypt / _decrypt, k_udp.hip) ----
+
+struct UdpShape {
+    uint64_t nconn, nsections;
+    int nr_data, nr_pkg;  // rounds of the two tables (nr_data: 0 without a data table)
+};
+
+// What the two calls check of their arguments before anything else (include/fpnn_aes.h), as
+// plain values: which pointers are there (addresses, for their alignment), the tables' sizes
+// and rounds.  Returns UDP_ARGS_OK, or the public error the call returns.
+struct UdpArgs {
+    bool key_slot;   // b->key_slot given
+    uint32_t flags;  // b->flags
+    bool u;          // the fpnn_aes_udp_data itself is there
+    bool data_keys, data_keys_same_engine;
+    uint32_t nconn, nsections, slot_bound;
+    uintptr_t first_dgram, conn_slot, iv_state, pos_state, first_section, sec_off, sec_len;
+    uint32_t pkg_slots, data_slots;  // capacity of b->keys and of data_keys
+    int nr_pkg, nr_data;             // their rounds
+};
+enum : int { UDP_ARGS_OK = 0, UDP_ARGS_KEYLEN = -1 /* FPNN_AES_ERR_KEYLEN */, UDP_ARGS_BAD = -2 /* FPNN_AES_ERR_ARG */ };
+
+inline int udp_check_args(const UdpArgs &a) {
+    if (a.key_slot || a.flags || !a.u) return UDP_ARGS_BAD;
+    if (a.data_keys ? !a.data_keys_same_engine : a.nsections != 0) return UDP_ARGS_BAD;
+    const auto bad4 = [](uintptr_t p) { return !p || (p & 3); };
+    if (a.nconn && (bad4(a.first_dgram) || bad4(a.conn_slot) || bad4(a.pos_state) || !a.iv_state || (a.iv_state & 15)))
+        return UDP_ARGS_BAD;
+    if (a.nsections && (bad4(a.first_section) || bad4(a.sec_off) || bad4(a.sec_len))) return UDP_ARGS_BAD;
+    if (a.first_section & 3) return UDP_ARGS_BAD;  // (optional without sections, aligned when given)
+    if (a.slot_bound > a.pkg_slots || (a.data_keys && a.slot_bound > a.data_slots)) return UDP_ARGS_BAD;
+    if (a.nr_pkg == 12 || (a.data_keys && a.nr_data == 12)) return UDP_ARGS_KEYLEN;
+    return UDP_ARGS_OK;
+}
+
+struct UdpRoute {
+    bool ok;              // both round counts are 10 or 14 (createPair makes 16- and 32-byte keys)
+    int nr_data, nr_pkg;  // encrypt: K2u's template arguments (without a data table: the package table's twice)
+    int threads, grid;    // encrypt: one quad per connection, sized as K2c is
+    // decrypt: the descriptors derived on the device, the package decrypt of the datagrams (one key
+    // slot each: decrypt_route with key_slot) and the slot-addressed *_frames decrypt of the
+    // sections, which are segments of `out` by offset and length arrays
+    DecryptRoute pkg;
+    ScratchNeed need;
+};
+
+inline bool udp_rounds_ok(int nr) { return nr == 10 || nr == 14; }
+
+// b: the datagram batch as the caller gave it (key_slot is null there)
+inline UdpRoute udp_route(const DispatchShape &d, const BatchShape &b, const UdpShape &u, bool encrypt) {
+    UdpRoute r = {};
+    r.nr_pkg = u.nr_pkg;
+    r.nr_data = u.nr_data ? u.nr_data : u.nr_pkg;
+    r.ok = udp_rounds_ok(r.nr_pkg) && udp_rounds_ok(r.nr_data);
+    if (!r.ok) return r;
+    if (encrypt) {
+        const Spread sp = spread_over_cus(d, 4 * u.nconn);
+        r.threads = sp.threads;
+        r.grid = sp.grid;
+        return r;
+    }
+    BatchShape pb = b;
+    pb.key_slot = true;
+    r.pkg = decrypt_route(d, pb, {false, false});
+    r.need = need_udp_decrypt(d.scratch, r.pkg.need, b.count, u.nsections, u.nconn);
+    return r;
+}
+
 }  // namespace fpnn_aes

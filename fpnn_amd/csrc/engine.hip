@@ -182,7 +182,8 @@ struct AuditExtents {
 // per stream; with state_slot (the _at calls) slot_bound entries, and state_slot[] and the
 // per-segment slot scratch are registered (the latter also as key_slot: K1r's view of it).
 int audit_begin(fpnn_aes_engine *e, const fpnn_aes_batch *b, const uint8_t *iv_state, const uint32_t *pos_state,
-                KBatch &k, const FrameTable *frames = nullptr) {
+                KBatch &k, const FrameTable *frames = nullptr, const UdpTable *udp = nullptr,
+                const fpnn_aes_keyset *data_keys = nullptr) {
     const uint64_t n = b->count;
     if (int rc = scratch_ensure(e, need_encrypt_ragged(scratch_shape(e), n, true))) return rc;
     HIP_TRY(hipStreamSynchronize(e->stream));  // (the descriptor arrays are read below)
@@ -203,6 +204,12 @@ int audit_begin(fpnn_aes_engine *e, const fpnn_aes_batch *b, const uint8_t *iv_s
         x.set(AB_STATE_SLOT, frames->state_slot, 4 * (uint64_t)frames->nstreams);
         x.set(AB_SEG_SLOT, frames->seg_slot, 4 * n);
         x.set(AB_SLOT, frames->seg_slot, 4 * n);
+    }
+    if (udp) {  // the UDP calls: frames names first_dgram[] and conn_slot[]
+        if (data_keys) x.set(AB_UDP_DATA_KEYS, udp->data_keys, sizeof(DevKey) * (uint64_t)table_slots(data_keys));
+        x.set(AB_UDP_FIRST_SECTION, udp->first_section, 4 * (n + 1));
+        x.set(AB_UDP_SEC_OFF, udp->sec_off, 4 * (uint64_t)udp->nsections);
+        x.set(AB_UDP_SEC_LEN, udp->sec_len, 4 * (uint64_t)udp->nsections);
     }
     x.set(AB_PERM, e->perm.p, 4 * n);
     x.set(AB_SINK, e->sink.p, 16 * e->sink.cap);
@@ -259,7 +266,8 @@ const char *audit_buf_name(uint32_t i) {
                                                   "iv_state", "pos_state", "perm", "sink", "length-order block",
                                                   "pos_snap", "in (outside its segment)", "out (outside its segment)",
                                                   "first_frame", "slots", "raw keys", "ivs", "ok", "state_slot",
-                                                  "segment slots"};
+                                                  "segment slots", "data keys", "first_section", "sec_off",
+                                                  "sec_len"};
     return i < kAuditBufs ? names[i] : "?";
 }
 
@@ -282,7 +290,7 @@ int audit_end(fpnn_aes_engine *e, int rc) {
 }
 #else  // the product build: no table, and audit_end(e, rc) is rc
 inline int audit_begin(fpnn_aes_engine *, const fpnn_aes_batch *, const uint8_t *, const uint32_t *, KBatch &,
-                       const FrameTable * = nullptr) {
+                       const FrameTable * = nullptr, const UdpTable * = nullptr, const fpnn_aes_keyset * = nullptr) {
     return FPNN_AES_OK;
 }
 inline int audit_begin_keytable(fpnn_aes_engine *, const fpnn_aes_keyset *, KeyTableArgs &) { return FPNN_AES_OK; }
@@ -562,6 +570,104 @@ int run_frames(fpnn_aes_engine *e, const fpnn_aes_batch *b, const uint32_t *firs
                                 : run_decrypt_frames_calls(e, b, first_frame, nstreams, iv_state, pos_state, at));
 }
 
+// ---- UDP v2 datagrams with data encryption (fpnn_aes_udp_encrypt / _decrypt, k_udp.hip) ----
+
+static_assert(UDP_ARGS_KEYLEN == FPNN_AES_ERR_KEYLEN && UDP_ARGS_BAD == FPNN_AES_ERR_ARG, "udp_check_args returns public errors");
+
+int check_udp(const fpnn_aes_engine *e, const fpnn_aes_batch *b, const fpnn_aes_udp_data *u) {
+    if (int rc = check_batch(e, b)) return rc;
+    UdpArgs a = {};
+    a.key_slot = b->key_slot != nullptr;
+    a.flags = b->flags;
+    a.u = u != nullptr;
+    a.pkg_slots = table_slots(b->keys);
+    a.nr_pkg = b->keys->nrounds;
+    if (u) {
+        a.data_keys = u->data_keys != nullptr;
+        if (u->data_keys) {
+            a.data_keys_same_engine = u->data_keys->e == e && u->data_keys->device == e->device;
+            a.data_slots = table_slots(u->data_keys);
+            a.nr_data = u->data_keys->nrounds;
+        }
+        a.nconn = u->nconn;
+        a.nsections = u->nsections;
+        a.slot_bound = u->slot_bound;
+        a.first_dgram = (uintptr_t)u->first_dgram;
+        a.conn_slot = (uintptr_t)u->conn_slot;
+        a.iv_state = (uintptr_t)u->iv_state;
+        a.pos_state = (uintptr_t)u->pos_state;
+        a.first_section = (uintptr_t)u->first_section;
+        a.sec_off = (uintptr_t)u->sec_off;
+        a.sec_len = (uintptr_t)u->sec_len;
+    }
+    return udp_check_args(a);
+}
+
+UdpTable udp_table(fpnn_aes_engine *e, const fpnn_aes_udp_data *u) {
+    return {u->data_keys ? u->data_keys->d_keys : nullptr, u->first_dgram, u->conn_slot, u->first_section, u->sec_off,
+            u->sec_len, u->nconn, u->slot_bound, u->nsections, 0u, e->d_fault};
+}
+
+UdpShape udp_shape(const fpnn_aes_batch *b, const fpnn_aes_udp_data *u) {
+    return {u->nconn, u->nsections, u->data_keys ? u->data_keys->nrounds : 0, b->keys->nrounds};
+}
+
+// Encrypt: K2u, one launch.
+int run_udp_encrypt_calls(fpnn_aes_engine *e, const fpnn_aes_batch *b, const fpnn_aes_udp_data *u) {
+    int rc = check_udp(e, b, u);
+    if (rc) return rc;
+    if (!u->nconn || !b->count) return FPNN_AES_OK;
+    DeviceGuard g(e->device);
+    const BatchScope batch_scope(e);  // (an early return clears the pending flag)
+    const UdpRoute r = udp_route(dispatch_shape(e), batch_shape(b), udp_shape(b, u), true);
+    if (!r.ok) return FPNN_AES_ERR_KEYLEN;
+    KBatch k = make_kbatch(e, b, u->iv_state, u->pos_state);
+    const UdpTable t = udp_table(e, u);
+    const FrameTable f{u->first_dgram, u->nconn, u->slot_bound, e->d_fault, u->conn_slot, nullptr};
+    if ((rc = audit_begin(e, b, u->iv_state, u->pos_state, k, &f, &t, u->data_keys))) return rc;
+    EventPair *ev;
+    if ((rc = timing_begin(e, FPNN_AES_K_ENCRYPT, &ev))) return rc;
+    HIP_TRY(launch_udp_encrypt(k, t, r.nr_data, r.nr_pkg, r.grid, r.threads, e->stream));
+    return timing_end(e, ev, FPNN_AES_K_ENCRYPT);
+}
+
+// Decrypt: both layers parallelise by block, so the call derives the descriptors the existing
+// kernels take (k_udp_expand, into scratch no other kernel of the call uses) and queues them in
+// order: the package decrypt of the datagrams in -> out with one key slot per datagram (K1k /
+// K1r / D2s by the dispatch plan), then the slot-addressed *_frames decrypt of the sections in
+// place in `out` under the data table (state pre-pass, K1r, commit).  The two steps share the
+// K1r scratch one after the other on the stream; its zeroed buffers are returned to zeros by
+// each step's own last reader.
+int run_udp_decrypt_calls(fpnn_aes_engine *e, const fpnn_aes_batch *b, const fpnn_aes_udp_data *u) {
+    int rc = check_udp(e, b, u);
+    if (rc) return rc;
+    if (!u->nconn || !b->count) return FPNN_AES_OK;
+    DeviceGuard g(e->device);
+    const UdpRoute r = udp_route(dispatch_shape(e), batch_shape(b), udp_shape(b, u), false);
+    if (!r.ok) return FPNN_AES_ERR_KEYLEN;
+    if ((rc = scratch_ensure(e, r.need))) return rc;
+    uint32_t *const dg_slot = e->udp_u32.p, *const sec_n = dg_slot + b->count, *const conn_sec = sec_n + u->nsections;
+    {
+        const BatchScope batch_scope(e);
+        const KBatch k = make_kbatch(e, b, u->iv_state, u->pos_state);
+        HIP_TRY(launch_udp_expand(k, udp_table(e, u), dg_slot, e->udp_off.p, sec_n, conn_sec, e->num_cus, e->stream));
+        batch_queued(e);
+    }
+    fpnn_aes_batch pb = *b;  // the datagrams, each under its connection's slot
+    pb.key_slot = dg_slot;
+    if ((rc = run_decrypt(e, &pb, nullptr, nullptr, false))) return rc;
+    if (!u->nsections) return FPNN_AES_OK;
+    fpnn_aes_batch sb;  // the sections: segments of `out`, in place
+    memset(&sb, 0, sizeof sb);
+    sb.in = sb.out = b->out;
+    sb.count = u->nsections;
+    sb.in_off = e->udp_off.p;
+    sb.len = sec_n;
+    sb.keys = u->data_keys;
+    const SlotAddr at{u->conn_slot, u->slot_bound, false};
+    return run_decrypt_frames_calls(e, &sb, conn_sec, u->nconn, u->iv_state, u->pos_state, &at);
+}
+
 }  // namespace
 
 int fpnn_aes::run_batch(fpnn_aes_engine *e, bool encrypt, const fpnn_aes_batch *b, uint8_t *iv_state,
@@ -818,6 +924,15 @@ int fpnn_aes_engine_reserve(fpnn_aes_engine *e, uint64_t max_segments, uint64_t 
     DeviceGuard g(e->device);
     // every call path at these bounds: calls within them then neither allocate nor memset
     return scratch_ensure(e, need_reserve(scratch_shape(e), max_segments, max_blocks));
+}
+
+uint64_t fpnn_aes_engine_scratch_bytes(fpnn_aes_engine *e) {
+    uint64_t bytes = 0;
+    if (!e) return 0;
+#define X(name, type, zeroed) bytes += e->name.cap * sizeof(type);
+    FPNN_AES_SCRATCH_BUFFERS(X)
+#undef X
+    return bytes;
 }
 
 // ---- key sets ---------------------------------------------------------------
@@ -1190,6 +1305,16 @@ int fpnn_aes_stream_decrypt_frames_at(fpnn_aes_engine *e, const fpnn_aes_batch *
                                       uint8_t *iv_state, uint32_t *pos_state) {
     const SlotAddr at{state_slot, slot_bound, false};
     return run_frames(e, b, first_frame, nstreams, iv_state, pos_state, false, &at);
+}
+
+// ---- UDP v2 datagrams with data encryption ---------------------------------------
+
+int fpnn_aes_udp_encrypt(fpnn_aes_engine *e, const fpnn_aes_batch *b, const fpnn_aes_udp_data *u) {
+    return audit_end(e, run_udp_encrypt_calls(e, b, u));
+}
+
+int fpnn_aes_udp_decrypt(fpnn_aes_engine *e, const fpnn_aes_batch *b, const fpnn_aes_udp_data *u) {
+    return audit_end(e, run_udp_decrypt_calls(e, b, u));
 }
 
 // ---- receive side: wire framing on the device ------------------------------------

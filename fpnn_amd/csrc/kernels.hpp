@@ -179,6 +179,32 @@ hipError_t launch_stream_frames_state(const KBatch &b, const FrameTable &f, int 
 // without one keeps its own.
 hipError_t launch_stream_frames_commit(const KBatch &b, const FrameTable &f, const uint4 *seg_iv,
                                        const uint32_t *seg_pos, hipStream_t st);
+// UDP v2 datagrams with data encryption (k_udp.hip; fpnn_aes_udp_encrypt / _decrypt).  The
+// KBatch describes the DATAGRAMS (b.keys: the package table; b.iv_state / b.pos_state: the data
+// StreamEncryptor's state, slot_bound entries); connection j owns datagrams [first_dgram[j],
+// first_dgram[j + 1]), datagram i sections [first_section[i], first_section[i + 1]), section s
+// the bytes [sec_off[s], + sec_len[s]) of its datagram.  conn_slot[j] names the connection's
+// slot in both tables and in the state arrays.  Both range tables have first_frame's contract
+// (FrameTable) and every kernel clamps what it reads from them; sections ascend inside their
+// datagram, and one that does not, or leaves it, is clamped into it and reported
+// (kFaultFrameTable).  A connection with conn_slot[j] >= slot_bound is reported
+// (kFaultKeySlot) and treated as a stream of the *_frames_at calls is.
+struct UdpTable {
+    const DevKey *data_keys;  // the data table's slots (null: the call has no section)
+    const uint32_t *first_dgram, *conn_slot;
+    const uint32_t *first_section, *sec_off, *sec_len;
+    uint32_t nconn, slot_bound, nsections, pad;
+    uint32_t *fault;
+};
+// K2u: encrypt, one quad per connection, data layer then package layer per datagram; grid and
+// threads sized as K2c's, by quads needed.  nr_data, nr_pkg: 10 or 14.
+hipError_t launch_udp_encrypt(const KBatch &b, const UdpTable &u, int nr_data, int nr_pkg, int grid, int threads,
+                              hipStream_t st);
+// Decrypt's descriptors for the existing kernels: dg_slot (count entries: every datagram's key
+// slot), sec_abs / sec_n (nsections: every section as a segment of b.out), conn_sec (nconn + 1:
+// every connection's section range).
+hipError_t launch_udp_expand(const KBatch &b, const UdpTable &u, uint32_t *dg_slot, uint64_t *sec_abs, uint32_t *sec_n,
+                             uint32_t *conn_sec, int num_cus, hipStream_t st);
 // K2h (k_hybrid.hip): ragged batches with more chains than quads.  Chains of perm[]
 // in length buckets <= long_bucket run on quads (K2c's cipher), the rest one per lane
 // (K2's); quad_waves waves per workgroup start on the long ones.  ctr: the 2 ticket

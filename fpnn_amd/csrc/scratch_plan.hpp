@@ -35,7 +35,9 @@ namespace fpnn_aes {
     X(sf_slot, uint32_t, false)   /* and (_at calls) its key slot */                                       \
     X(lookback, uint64_t, true)  /* one-pass block map: tickets, epoch, tile status */                     \
     X(ecdh, uint8_t, false)      /* ECDH: peers | keys | ivs | ok, bytes (wiped by every call: ecdh_wipe) */ \
-    X(sstate, uint8_t, false)    /* stream host frames: (iv, pos) of the call's streams, bytes */
+    X(sstate, uint8_t, false)    /* stream host frames: (iv, pos) of the call's streams, bytes */              \
+    X(udp_off, uint64_t, false)  /* UDP decrypt: every section as a segment of `out`, its offset */          \
+    X(udp_u32, uint32_t, false)  /* and: datagram key slots | section lengths | connection section ranges */
 
 enum ScratchId {
 #define X(name, type, zeroed) SC_##name,
@@ -113,6 +115,19 @@ inline ScratchNeed need_ecdh_accept(uint64_t count, uint64_t keylen) {
     return r;
 }
 
+// fpnn_aes_udp_decrypt of `dgrams` datagrams and `sections` data sections of `conns` connections: the
+// derived descriptors (k_udp.hip, k_udp_expand), the package decrypt of the datagrams on its route
+// (pkg: decrypt_route's need) and the slot-addressed *_frames decrypt of the sections, whose
+// descriptor arrays are the derived ones.  fpnn_aes_udp_encrypt (K2u) needs no scratch.
+inline ScratchNeed need_udp_decrypt(const ScratchShape &s, const ScratchNeed &pkg, uint64_t dgrams, uint64_t sections,
+                                    uint64_t conns) {
+    ScratchNeed r = pkg;
+    r.n[SC_udp_off] = sections;
+    r.n[SC_udp_u32] = dgrams + sections + conns + 1;
+    if (sections) r = scratch_max(r, need_decrypt_frames(s, sections, true, true, true));
+    return r;
+}
+
 // fpnn_aes_engine_reserve: every path above at its bounds.  Two entries exceed the maximum, as
 // reserve has always given them: look-back words also below small_max, one more boundary entry.
 inline ScratchNeed need_reserve(const ScratchShape &s, uint64_t max_segments, uint64_t max_blocks) {
@@ -121,6 +136,8 @@ inline ScratchNeed need_reserve(const ScratchShape &s, uint64_t max_segments, ui
     r = scratch_max(r, need_encrypt_ragged(s, max_segments, true));
     r = scratch_max(r, need_decrypt_dense_inplace(max_blocks));
     r = scratch_max(r, need_ecdh_accept(max_segments, 32));
+    // (the UDP decrypt's package step is a ragged or an in-place dense decrypt: both are above)
+    r = scratch_max(r, need_udp_decrypt(s, ScratchNeed{}, max_segments, max_segments, max_segments));
     r.n[SC_lookback] = s.onepass_words(max_segments);
     r.n[SC_boundary] += 1;
     return r;

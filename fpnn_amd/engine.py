@@ -23,8 +23,8 @@ import numpy as np
 
 import torch
 
-from ._lib import (BatchDesc, FpnnAesError, HostFrame, Schedule, check, lib, F_WIRE_PREFIX, K_DECRYPT, K_ENCRYPT,
-                   ERR_KEYLEN, OK)
+from ._lib import (BatchDesc, FpnnAesError, HostFrame, Schedule, UdpData, check, lib, F_WIRE_PREFIX, K_DECRYPT,
+                   K_ENCRYPT, ERR_KEYLEN, OK)
 
 
 def _buf(b: bytes):
@@ -120,6 +120,10 @@ class Engine:
 
     def reserve(self, max_segments: int, max_blocks: int):
         check(lib.fpnn_aes_engine_reserve(self._h, max_segments, max_blocks), "reserve")
+
+    def scratch_bytes(self) -> int:
+        """Bytes of device scratch the engine holds (fpnn_aes_engine_scratch_bytes)."""
+        return int(lib.fpnn_aes_engine_scratch_bytes(self._h))
 
     # -- timing -----------------------------------------------------------------------
     def set_timing(self, enable: bool):
@@ -493,6 +497,46 @@ class Engine:
                           state_slot: torch.Tensor, slot_bound: int, **kw):
         self._one_frame_at(lib.fpnn_aes_stream_decrypt_at, "stream_decrypt_at", inp, out, count, keys, iv_state,
                            pos_state, state_slot, slot_bound, kw)
+
+    # UDP v2 datagrams with data encryption (fpnn_aes_udp_encrypt / _decrypt): the batch describes
+    # the datagrams under the package table `keys`; connection j owns datagrams [first_dgram[j],
+    # first_dgram[j+1]), datagram i sections [first_section[i], first_section[i+1]) at sec_off /
+    # sec_len inside it; conn_slot[j] names the connection's slot in `keys`, in `data_keys` and in
+    # the state arrays (slot_bound entries: the data StreamEncryptor's state).
+    def _udp(self, fn, what, inp, out, count, keys, data_keys, nconn, first_dgram, conn_slot, slot_bound, nsections,
+             first_section, sec_off, sec_len, iv_state, pos_state, kw):
+        d = self._desc(inp, out, count, keys, **kw)
+        for name, t, n in (("first_dgram", first_dgram, nconn + 1), ("conn_slot", conn_slot, nconn),
+                           ("first_section", first_section, count + 1), ("sec_off", sec_off, nsections),
+                           ("sec_len", sec_len, nsections)):
+            if t is not None:
+                if t.dtype not in (torch.int32, torch.uint32):
+                    raise TypeError(f"{name}: dtype {t.dtype}, expected {torch.int32}")
+                if t.numel() < n:
+                    raise ValueError(f"{name}: {t.numel()} entries, {n} needed")
+        u = UdpData()
+        u.data_keys = data_keys.handle.value if data_keys is not None else None
+        u.nconn = nconn
+        u.slot_bound = slot_bound
+        u.nsections = nsections
+        for name, t in (("first_dgram", first_dgram), ("conn_slot", conn_slot), ("first_section", first_section),
+                        ("sec_off", sec_off), ("sec_len", sec_len), ("iv_state", iv_state), ("pos_state", pos_state)):
+            setattr(u, name, _ptr(t).value if t is not None else None)
+        check(fn(self._h, C.byref(d), C.byref(u)), what)
+
+    def udp_encrypt(self, inp, out, count, keys: "KeySet", data_keys: Optional["KeySet"], nconn: int,
+                    first_dgram: torch.Tensor, conn_slot: torch.Tensor, slot_bound: int, nsections: int,
+                    first_section: Optional[torch.Tensor], sec_off: Optional[torch.Tensor],
+                    sec_len: Optional[torch.Tensor], iv_state: torch.Tensor, pos_state: torch.Tensor, **kw):
+        self._udp(lib.fpnn_aes_udp_encrypt, "udp_encrypt", inp, out, count, keys, data_keys, nconn, first_dgram,
+                  conn_slot, slot_bound, nsections, first_section, sec_off, sec_len, iv_state, pos_state, kw)
+
+    def udp_decrypt(self, inp, out, count, keys: "KeySet", data_keys: Optional["KeySet"], nconn: int,
+                    first_dgram: torch.Tensor, conn_slot: torch.Tensor, slot_bound: int, nsections: int,
+                    first_section: Optional[torch.Tensor], sec_off: Optional[torch.Tensor],
+                    sec_len: Optional[torch.Tensor], iv_state: torch.Tensor, pos_state: torch.Tensor, **kw):
+        self._udp(lib.fpnn_aes_udp_decrypt, "udp_decrypt", inp, out, count, keys, data_keys, nconn, first_dgram,
+                  conn_slot, slot_bound, nsections, first_section, sec_off, sec_len, iv_state, pos_state, kw)
 
 
 def host_register(buf: np.ndarray):

@@ -92,6 +92,10 @@ void *fpnn_aes_engine_stream(fpnn_aes_engine *e);
  * per-segment scratch is sized from max_segments as well, and so is the scratch of
  * fpnn_ecdh_accept (fpnn_ecdh.h) for up to max_segments peers per call. */
 int fpnn_aes_engine_reserve(fpnn_aes_engine *e, uint64_t max_segments, uint64_t max_blocks);
+/* Bytes of device scratch the engine holds now (every growing buffer's capacity; 0 for NULL).
+ * It changes only when a call grows a buffer: equal values before and after a call mean the
+ * call allocated no scratch, which is what fpnn_aes_engine_reserve promises within its bounds. */
+uint64_t fpnn_aes_engine_scratch_bytes(fpnn_aes_engine *e);
 
 /* Placement of the engines behind the C++ classes (Encryptor, EncryptorBatch,
  * StreamReceiverBatch, ECCKeyExchange): one pool per process, engine k created on the
@@ -326,6 +330,66 @@ int fpnn_aes_stream_encrypt_at(fpnn_aes_engine *e, const fpnn_aes_batch *b,
 int fpnn_aes_stream_decrypt_at(fpnn_aes_engine *e, const fpnn_aes_batch *b,
         const uint32_t *state_slot, uint32_t slot_bound,
         uint8_t *iv_state, uint32_t *pos_state);
+
+/* ---- UDP v2 datagrams with data ("enhanced") encryption ------------------------------ */
+/* A UDPEncryptor with reinforced data encryption holds two ciphers (core/UDP.v2/
+ * UDPCommon.v2.h:100-129, UDPCommon.v2.cpp:146-215): a StreamEncryptor under the data key
+ * ciphers each non-discardable data section as the assembler places it into the datagram --
+ * ONE CFB chain through the connection's whole life (UDPAssembler.v2.cpp:575-578, 619-622,
+ * 698-701) -- and a PackageEncryptor under the package key then ciphers the whole datagram
+ * with a fresh chain from the connection IV (UDPIOBuffer.v2.cpp:351); the receiver undoes
+ * them in the opposite order (UDPParser.v2.cpp:91, then :702, :773, :827 per section).
+ *
+ * b describes the DATAGRAMS, as any batch (anywhere, gaps allowed, in place when in == out;
+ * bytes of out outside the datagrams are not touched); b->keys is the package table and
+ * b->key_slot must be NULL: connection j's slot conn_slot[j] names its key and IV in b->keys,
+ * its data key in data_keys, and its entry of the state arrays, which hold the data
+ * StreamEncryptor's (_iv, _pos) (fpnn_aes_stream_open on data_keys starts them).  The result
+ * is bit for bit the reference's: per connection the datagrams in order, per datagram the
+ * sections in order; encrypt = dataEncrypt(section) continuing the slot's state, then
+ * packageEncrypt(datagram); decrypt = packageDecrypt(datagram), then dataDecrypt(section).
+ * The state is updated in place; slots not named, connections without datagrams and
+ * connections whose sections are all empty keep every bit of it.  Datagrams without
+ * sections, zero-length datagrams and zero-length sections are legal.  The two tables may
+ * have different key lengths, 16 or 32 bytes each (FPNN_AES_ERR_KEYLEN for a 24-byte table).
+ *
+ * first_dgram and first_section have first_frame's contract (non-decreasing, from 0, ending
+ * at b->count / nsections); inside a datagram the sections ascend, do not overlap and lie
+ * inside it.  Input that breaks this never makes a kernel leave the datagram's own bytes
+ * (what is read is clamped): that connection's results are invalid and the next
+ * fpnn_aes_engine_sync returns FPNN_AES_ERR_DEVICE once.  conn_slot[j] >= slot_bound is
+ * treated as by fpnn_aes_stream_*_frames_at: the connection's state is not touched, encrypt
+ * writes nothing for it, decrypt leaves its own output bytes unspecified, all other
+ * connections are exact, FPNN_AES_ERR_DEVICE once.
+ *
+ * FPNN_AES_ERR_ARG: b->key_slot not NULL, b->flags not 0, u NULL; data_keys NULL with
+ * nsections != 0, or made on another engine; with nconn != 0, NULL or misaligned
+ * first_dgram, conn_slot, iv_state (16 bytes) or pos_state; with nsections != 0, NULL or
+ * misaligned first_section, sec_off or sec_len; slot_bound above the capacity of either
+ * table.  nconn == 0 or b->count == 0 queues nothing.  Both calls are queued on the engine's
+ * stream with no host wait; after fpnn_aes_engine_reserve(max_segments, max_blocks) with
+ * max_segments >= max(b->count, nsections, nconn) they allocate nothing.
+ *
+ * Encrypt is one kernel (K2u: one lane quad per connection, both key schedules and the data
+ * layer's state in registers; no intermediate copy of the batch).  Decrypt queues the
+ * package decrypt of the datagrams and the slot-addressed *_frames decrypt of the sections,
+ * in place in out, behind one small kernel that derives their descriptors on the device. */
+typedef struct {
+    const fpnn_aes_keyset *data_keys;  /* data keys (+ data IVs), one key length (16 or 32), same engine */
+    uint32_t nconn;                    /* connections in this call */
+    const uint32_t *first_dgram;       /* dev, nconn+1: connection j owns datagrams [first_dgram[j], first_dgram[j+1]) of b, in send order */
+    const uint32_t *conn_slot;         /* dev, nconn: slot of b->keys, of data_keys AND of the state arrays */
+    uint32_t slot_bound;
+    uint32_t nsections;
+    const uint32_t *first_section;     /* dev, b->count+1: datagram i owns sections [first_section[i], first_section[i+1]) */
+    const uint32_t *sec_off;           /* dev, nsections: byte offset inside its datagram */
+    const uint32_t *sec_len;           /* dev, nsections */
+    uint8_t  *iv_state;                /* dev, 16*slot_bound, 16-byte aligned: the data StreamEncryptor's _iv */
+    uint32_t *pos_state;               /* dev, slot_bound: its _pos */
+} fpnn_aes_udp_data;
+
+int fpnn_aes_udp_encrypt(fpnn_aes_engine *e, const fpnn_aes_batch *b, const fpnn_aes_udp_data *u);
+int fpnn_aes_udp_decrypt(fpnn_aes_engine *e, const fpnn_aes_batch *b, const fpnn_aes_udp_data *u);
 
 /* ---- single call from host memory (the per-frame drop-in) --------------------------- */
 /* Exactly rijndael_cfb_encrypt(ctx, encrypt, in, out, len, ivec, p_num)

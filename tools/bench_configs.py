@@ -14,6 +14,9 @@ for DESIGN.md -- bench.py's single JSON line covers C2 only.
   C4A one frame per stream by key-table slot, C4's length law over 2^18 streams, AES-256 per-slot keys:
       fpnn_aes_stream_encrypt_at (K2h) against fpnn_aes_stream_encrypt_frames_at (K2f)   (on request)
   S1A S1 through fpnn_aes_stream_host_at (state in device arrays by table slot)          (on request)
+  U2  U1's datagrams with the data layer, 16384 connections x 64 datagrams, section [12, 1472), AES-128
+      package + AES-256 data keys: fpnn_aes_udp_* against the same work composed from the older calls
+      and against the data chain alone; U2c: 262144 connections x 4 datagrams              (on request)
 """
 import argparse
 import json
@@ -308,6 +311,83 @@ def main():
                      "datagrams_per_s_encrypt_kernel": round(P / ke)}
         del a, b, r
         print(json.dumps({"U1": out["U1"]}), flush=True)
+
+    for uname in [u for u in ("U2", "U2c") if u in todo]:
+        # U1's datagrams with the data layer (fpnn_aes_udp_encrypt / _decrypt): every datagram one
+        # data section [12, 1472) behind the 8-byte package header and the 4-byte section header,
+        # AES-128 package keys and AES-256 data keys; connection j owns datagrams [j*DG, (j+1)*DG).
+        # Three figures per direction, wall time per call, all in GiB/s of DATAGRAM bytes:
+        #   fused     the one call
+        #   composed  the same work from the calls that existed before it: device copy in -> tmp,
+        #             stream_*_frames_at over the sections in tmp, package_* tmp -> out
+        #             (decrypt: package_decrypt in -> out, stream_decrypt_frames_at in place)
+        #   floor     stream_*_frames_at over the sections alone: what the data chain costs
+        c = W.U1
+        P, L = c["packets"], c["length"]
+        NC = 16384 if uname == "U2" else 262144
+        DG = P // NC
+        pk, piv = W.many_keys(dict(c, connections=NC))
+        dk, div = W.many_keys(dict(c, connections=NC, keylen=32, key_seed=c["key_seed"] + 1))
+        ksp = fpnn_amd.KeySet(eng, pk.tobytes(), 16, piv.tobytes())
+        ksd = fpnn_amd.KeySet(eng, dk.tobytes(), 32, div.tobytes())
+        i32 = lambda t: t.to(torch.int32).contiguous()  # noqa: E731
+        ar = lambda n: torch.arange(n, dtype=torch.int64, device="cuda")  # noqa: E731
+        first_dgram, conn_slot, first_section = i32(ar(NC + 1) * DG), i32(ar(NC)), i32(ar(P + 1))
+        sec_off = torch.full((P,), 12, dtype=torch.int32, device="cuda")
+        sec_len = torch.full((P,), L - 12, dtype=torch.int32, device="cuda")
+        sec_abs = (ar(P) * L + 12).contiguous()
+        dg_slot = i32(ar(P) // DG)
+        a = torch.empty(P * L, dtype=torch.uint8, device="cuda")
+        eng.fill_synthetic(a, c["payload_seed"])
+        b, tmp, r = torch.empty_like(a), torch.empty_like(a), torch.empty_like(a)
+        iv0 = torch.from_numpy(div.copy()).cuda()
+        iv_s, pos_s = iv0.clone(), torch.zeros(NC, dtype=torch.int32, device="cuda")
+
+        def reset():
+            iv_s.copy_(iv0)
+            pos_s.zero_()
+
+        def fused(fn, src, dst):
+            fn(src, dst, P, ksp, ksd, NC, first_dgram, conn_slot, NC, P, first_section, sec_off, sec_len, iv_s, pos_s,
+               stride=L, uniform_len=L)
+
+        def sections(fn, buf):
+            fn(buf, buf, P, ksd, iv_s, pos_s, first_dgram, NC, conn_slot, NC, in_off=sec_abs, lens=sec_len)
+
+        def composed_enc():
+            tmp.copy_(a)
+            sections(eng.stream_encrypt_frames_at, tmp)
+            eng.package_encrypt(tmp, r, P, ksp, stride=L, uniform_len=L, key_slot=dg_slot)
+
+        def composed_dec():
+            eng.package_decrypt(b, r, P, ksp, stride=L, uniform_len=L, key_slot=dg_slot)
+            sections(eng.stream_decrypt_frames_at, r)
+
+        # the two ways agree, from the same state, before anything is timed
+        reset()
+        fused(eng.udp_encrypt, a, b)
+        reset()
+        composed_enc()
+        assert torch.equal(b, r), uname + ": fused and composed ciphertext differ"
+        reset()
+        fused(eng.udp_decrypt, b, tmp)
+        assert torch.equal(tmp, a), uname + ": decrypt(encrypt(x)) != x"
+        res = {}
+        for name, fn, which in (("encrypt_fused", lambda: fused(eng.udp_encrypt, a, b), E),
+                                ("encrypt_composed", composed_enc, E),
+                                ("encrypt_floor", lambda: sections(eng.stream_encrypt_frames_at, tmp), E),
+                                ("decrypt_fused", lambda: fused(eng.udp_decrypt, b, r), D),
+                                ("decrypt_composed", composed_dec, D),
+                                ("decrypt_floor", lambda: sections(eng.stream_decrypt_frames_at, tmp), D)):
+            w, k, _ = timed(eng, which, fn, args.reps)
+            res[name + "_wall_GiBs"] = gib(P * L, w)
+            if name == "encrypt_fused":
+                res["encrypt_fused_kernel_GiBs"] = gib(P * L, k)
+        for d in ("encrypt", "decrypt"):
+            res[d + "_fused_over_composed"] = round(res[d + "_fused_wall_GiBs"] / res[d + "_composed_wall_GiBs"], 3)
+        out[uname] = res
+        del a, b, tmp, r
+        print(json.dumps({uname: res}), flush=True)
 
     for qname in [q for q in ("Q1", "Q1g", "Q1s", "Q1h") if q in todo]:
         # FPNN's typical quest frames (145 B: core/test/tcp-test/asyncStressClient.cpp:13-29)
