@@ -93,6 +93,32 @@ class UdpData(C.Structure):
     ]
 
 
+class UdpScan(C.Structure):
+    """fpnn_aes_udp_scan (include/fpnn_aes.h): one per datagram."""
+
+    _fields_ = [("pkgs", C.c_uint16), ("sections", C.c_uint16), ("version", C.c_uint8), ("status", C.c_uint8),
+                ("reserved", C.c_uint16)]
+
+
+class UdpPkg(C.Structure):
+    """fpnn_aes_udp_pkg (include/fpnn_aes.h): one per package walked."""
+
+    _fields_ = [("seq", C.c_uint32), ("type", C.c_uint8), ("flag", C.c_uint8), ("sign", C.c_uint8),
+                ("status", C.c_uint8), ("off", C.c_uint16), ("len", C.c_uint16), ("first_section", C.c_uint16),
+                ("nsections", C.c_uint16)]
+
+
+class UdpSection(C.Structure):
+    """fpnn_aes_udp_section (include/fpnn_aes.h): one per component walked."""
+
+    _fields_ = [("type", C.c_uint8), ("flag", C.c_uint8), ("pkg", C.c_uint16), ("off", C.c_uint16),
+                ("len", C.c_uint16), ("package_id", C.c_uint16), ("reserved", C.c_uint16), ("seg_index", C.c_uint32)]
+
+
+# fpnn_aes_udp_recv's flags and the FPNN_AES_UDP_* statuses of the walk tables
+UDP_F_WALK_ONLY, UDP_F_PLAIN = 1, 2
+UDP_OK, UDP_SHORT, UDP_VERSION, UDP_TYPE, UDP_ACKS, UDP_CLOSE, UDP_FULL, UDP_LONG = range(8)
+
 _vp = C.c_void_p
 _u8p = C.POINTER(C.c_uint8)
 
@@ -146,6 +172,10 @@ SIGNATURES = {
                                                     _vp]),
     "fpnn_aes_udp_encrypt": (C.c_int, [_vp, C.POINTER(BatchDesc), C.POINTER(UdpData)]),
     "fpnn_aes_udp_decrypt": (C.c_int, [_vp, C.POINTER(BatchDesc), C.POINTER(UdpData)]),
+    "fpnn_aes_udp_recv": (C.c_int, [_vp, C.POINTER(BatchDesc), C.POINTER(UdpData), C.c_uint32, C.c_uint32, C.c_uint32,
+                                    _vp, _vp, _vp]),
+    "fpnn_aes_udp_recv_take": (C.c_int, [_vp, C.POINTER(BatchDesc), C.POINTER(UdpData), C.c_uint32, C.c_uint32, _vp,
+                                         _vp, _vp, _vp, _vp, C.c_uint32]),
     "fpnn_aes_cfb_host": (C.c_int, [_vp, C.POINTER(Schedule), C.c_int, _vp, _vp, C.c_size_t, _u8p,
                                     C.POINTER(C.c_size_t)]),
     "fpnn_aes_package_host": (C.c_int, [_vp, C.c_int, C.POINTER(HostFrame), C.c_uint32, _vp, C.c_uint32]),

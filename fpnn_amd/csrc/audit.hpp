@@ -3,9 +3,11 @@
 //
 // Every global load and store of K2h (k_hybrid.hip), K2's ragged path (k_encrypt.hip), the
 // length-order kernels (k_support.hip), the many-frames-per-stream kernels
-// (k_stream_frames.hip: the caller's arrays and the payload) and the key-table kernels
-// (k_keytable.hip: the caller's arrays, the DevKey slots, eiv[] and the stream state) names the buffer it
-// indexes through FA_AT / FA_SEG / FA_RG.  In the audit build each one checks its byte range against an extent:
+// (k_stream_frames.hip: the caller's arrays and the payload), the key-table kernels
+// (k_keytable.hip: the caller's arrays, the DevKey slots, eiv[] and the stream state) and the UDP
+// kernels (k_udp.hip; k_udp_recv.hip: the datagram bytes the walk reads, the walk tables, the take
+// lists) names the buffer it indexes through FA_AT / FA_SEG / FA_RG.  In the audit build each one
+// checks its byte range against an extent:
 //   * the array extents the host supplies per call (AuditTable::lo/hi: descriptor arrays of
 //     `count` entries, the key set's slots, perm[] of `count` entries, the wave sinks, the
 //     length-order block, the stream state arrays, and the union of the segments' payload);
@@ -52,6 +54,11 @@ enum AuditBuf : uint32_t {
     AB_UDP_FIRST_SECTION,  // first_section[], count + 1 entries,
     AB_UDP_SEC_OFF,        // sec_off[] and sec_len[], nsections entries each (first_dgram[] and
     AB_UDP_SEC_LEN,        // conn_slot[] are checked as AB_FIRST_FRAME and AB_STATE_SLOT)
+    AB_UDP_SCAN,           // the UDP receive calls (k_udp_recv.hip): scan[], count entries,
+    AB_UDP_PKGS,           // pkgs[], count * max_pkgs, sections[], count * max_sections,
+    AB_UDP_SECTIONS,
+    AB_UDP_FIRST_TAKE,     // first_take[], nconn + 1, and take[], ntake entries
+    AB_UDP_TAKE,
     kAuditBufs
 };
 

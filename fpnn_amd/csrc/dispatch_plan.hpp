@@ -329,4 +329,60 @@ inline UdpRoute udp_route(const DispatchShape &d, const BatchShape &b, const Udp
     return r;
 }
 
+// ---- UDP v2 receive (fpnn_aes_udp_recv / _recv_take, k_udp_recv.hip) ----
+
+enum : uint32_t { UDP_F_WALK_ONLY = 1u /* FPNN_AES_UDP_F_WALK_ONLY */, UDP_F_PLAIN = 2u /* FPNN_AES_UDP_F_PLAIN */ };
+
+// What the two calls check beyond udp_check_args (include/fpnn_aes.h), as plain values.  take:
+// fpnn_aes_udp_recv_take (flags 0).
+struct UdpRecvArgs {
+    UdpArgs udp;  // the batch and the fpnn_aes_udp_data, as for fpnn_aes_udp_decrypt
+    bool take;
+    uint32_t flags;
+    bool in_place;  // b->in == b->out and no b->out_off
+    uint32_t count, max_pkgs, max_sections, ntake;
+    uintptr_t scan, pkgs, sections, first_take, take_list;
+};
+
+inline int udp_recv_check_args(const UdpRecvArgs &a) {
+    // the sections are outputs: none may come in (checked first: udp_check_args would accept them)
+    if (a.udp.u && (a.udp.nsections || a.udp.first_section || a.udp.sec_off || a.udp.sec_len)) return UDP_ARGS_BAD;
+    if (const int rc = udp_check_args(a.udp); rc == UDP_ARGS_BAD) return rc;
+    if (a.flags & ~(UDP_F_WALK_ONLY | UDP_F_PLAIN)) return UDP_ARGS_BAD;
+    if (a.take && a.flags) return UDP_ARGS_BAD;
+    if ((a.flags & UDP_F_PLAIN) && !a.in_place) return UDP_ARGS_BAD;
+    if (!a.udp.data_keys && !(a.flags & UDP_F_WALK_ONLY)) return UDP_ARGS_BAD;
+    if (!a.max_pkgs || !a.max_sections) return UDP_ARGS_BAD;
+    if ((uint64_t)a.count * a.max_pkgs > UINT32_MAX || (uint64_t)a.count * a.max_sections > UINT32_MAX)
+        return UDP_ARGS_BAD;
+    if (a.take && (uint64_t)a.ntake * a.max_sections > UINT32_MAX) return UDP_ARGS_BAD;
+    if (a.count && (!a.scan || (a.scan & 1) || !a.pkgs || (a.pkgs & 3) || !a.sections || (a.sections & 3)))
+        return UDP_ARGS_BAD;
+    if (a.ntake && (!a.first_take || (a.first_take & 3) || !a.take_list || (a.take_list & 3))) return UDP_ARGS_BAD;
+    return udp_check_args(a.udp);  // (OK or KEYLEN: an argument error comes before a key length's)
+}
+
+struct UdpRecvRoute {
+    bool ok;          // as UdpRoute::ok
+    bool package;     // the package decrypt of the datagrams runs (not PLAIN, not recv_take)
+    bool data;        // the data decrypt runs (not WALK_ONLY)
+    uint64_t nseg;    // its segments: max_sections per datagram, or per taken package
+    DecryptRoute pkg; // the package decrypt's route: udp_route's
+    ScratchNeed need;
+};
+
+// b: the datagram batch as the caller gave it
+inline UdpRecvRoute udp_recv_route(const DispatchShape &d, const BatchShape &b, const UdpShape &u, bool take,
+                                   uint32_t flags, uint32_t max_sections, uint32_t ntake) {
+    UdpRecvRoute r = {};
+    r.package = !take && !(flags & UDP_F_PLAIN);
+    r.data = !(flags & UDP_F_WALK_ONLY);
+    r.ok = udp_rounds_ok(u.nr_pkg) && (!u.nr_data || udp_rounds_ok(u.nr_data));
+    if (!r.ok) return r;
+    r.nseg = r.data ? (uint64_t)(take ? ntake : b.count) * max_sections : 0;
+    if (r.package) r.pkg = udp_route(d, b, {u.nconn, 0, u.nr_data, u.nr_pkg}, false).pkg;
+    r.need = need_udp_decrypt(d.scratch, r.pkg.need, r.package ? b.count : 0, r.nseg, u.nconn);
+    return r;
+}
+
 }  // namespace fpnn_aes

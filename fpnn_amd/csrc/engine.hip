@@ -183,7 +183,7 @@ struct AuditExtents {
 // per-segment slot scratch are registered (the latter also as key_slot: K1r's view of it).
 int audit_begin(fpnn_aes_engine *e, const fpnn_aes_batch *b, const uint8_t *iv_state, const uint32_t *pos_state,
                 KBatch &k, const FrameTable *frames = nullptr, const UdpTable *udp = nullptr,
-                const fpnn_aes_keyset *data_keys = nullptr) {
+                const fpnn_aes_keyset *data_keys = nullptr, const UdpRecvTable *recv = nullptr) {
     const uint64_t n = b->count;
     if (int rc = scratch_ensure(e, need_encrypt_ragged(scratch_shape(e), n, true))) return rc;
     HIP_TRY(hipStreamSynchronize(e->stream));  // (the descriptor arrays are read below)
@@ -210,6 +210,13 @@ int audit_begin(fpnn_aes_engine *e, const fpnn_aes_batch *b, const uint8_t *iv_s
         x.set(AB_UDP_FIRST_SECTION, udp->first_section, 4 * (n + 1));
         x.set(AB_UDP_SEC_OFF, udp->sec_off, 4 * (uint64_t)udp->nsections);
         x.set(AB_UDP_SEC_LEN, udp->sec_len, 4 * (uint64_t)udp->nsections);
+    }
+    if (recv) {  // the UDP receive calls: the walk tables and the take lists
+        x.set(AB_UDP_SCAN, recv->scan, sizeof(UdpScan) * n);
+        x.set(AB_UDP_PKGS, recv->pkgs, sizeof(UdpPkg) * n * recv->max_pkgs);
+        x.set(AB_UDP_SECTIONS, recv->sections, sizeof(UdpSection) * n * recv->max_sections);
+        x.set(AB_UDP_FIRST_TAKE, recv->first_take, 4 * ((uint64_t)frames->nstreams + 1));
+        x.set(AB_UDP_TAKE, recv->take, 4 * (uint64_t)recv->ntake);
     }
     x.set(AB_PERM, e->perm.p, 4 * n);
     x.set(AB_SINK, e->sink.p, 16 * e->sink.cap);
@@ -267,7 +274,7 @@ const char *audit_buf_name(uint32_t i) {
                                                   "pos_snap", "in (outside its segment)", "out (outside its segment)",
                                                   "first_frame", "slots", "raw keys", "ivs", "ok", "state_slot",
                                                   "segment slots", "data keys", "first_section", "sec_off",
-                                                  "sec_len"};
+                                                  "sec_len", "scan", "pkgs", "sections", "first_take", "take"};
     return i < kAuditBufs ? names[i] : "?";
 }
 
@@ -290,7 +297,8 @@ int audit_end(fpnn_aes_engine *e, int rc) {
 }
 #else  // the product build: no table, and audit_end(e, rc) is rc
 inline int audit_begin(fpnn_aes_engine *, const fpnn_aes_batch *, const uint8_t *, const uint32_t *, KBatch &,
-                       const FrameTable * = nullptr, const UdpTable * = nullptr, const fpnn_aes_keyset * = nullptr) {
+                       const FrameTable * = nullptr, const UdpTable * = nullptr, const fpnn_aes_keyset * = nullptr,
+                       const UdpRecvTable * = nullptr) {
     return FPNN_AES_OK;
 }
 inline int audit_begin_keytable(fpnn_aes_engine *, const fpnn_aes_keyset *, KeyTableArgs &) { return FPNN_AES_OK; }
@@ -574,8 +582,7 @@ int run_frames(fpnn_aes_engine *e, const fpnn_aes_batch *b, const uint32_t *firs
 
 static_assert(UDP_ARGS_KEYLEN == FPNN_AES_ERR_KEYLEN && UDP_ARGS_BAD == FPNN_AES_ERR_ARG, "udp_check_args returns public errors");
 
-int check_udp(const fpnn_aes_engine *e, const fpnn_aes_batch *b, const fpnn_aes_udp_data *u) {
-    if (int rc = check_batch(e, b)) return rc;
+UdpArgs udp_args(const fpnn_aes_engine *e, const fpnn_aes_batch *b, const fpnn_aes_udp_data *u) {
     UdpArgs a = {};
     a.key_slot = b->key_slot != nullptr;
     a.flags = b->flags;
@@ -600,7 +607,12 @@ int check_udp(const fpnn_aes_engine *e, const fpnn_aes_batch *b, const fpnn_aes_
         a.sec_off = (uintptr_t)u->sec_off;
         a.sec_len = (uintptr_t)u->sec_len;
     }
-    return udp_check_args(a);
+    return a;
+}
+
+int check_udp(const fpnn_aes_engine *e, const fpnn_aes_batch *b, const fpnn_aes_udp_data *u) {
+    if (int rc = check_batch(e, b)) return rc;
+    return udp_check_args(udp_args(e, b, u));
 }
 
 UdpTable udp_table(fpnn_aes_engine *e, const fpnn_aes_udp_data *u) {
@@ -661,6 +673,97 @@ int run_udp_decrypt_calls(fpnn_aes_engine *e, const fpnn_aes_batch *b, const fpn
     memset(&sb, 0, sizeof sb);
     sb.in = sb.out = b->out;
     sb.count = u->nsections;
+    sb.in_off = e->udp_off.p;
+    sb.len = sec_n;
+    sb.keys = u->data_keys;
+    const SlotAddr at{u->conn_slot, u->slot_bound, false};
+    return run_decrypt_frames_calls(e, &sb, conn_sec, u->nconn, u->iv_state, u->pos_state, &at);
+}
+
+// ---- UDP v2 receive (fpnn_aes_udp_recv / _recv_take, k_udp_recv.hip) ----
+
+static_assert(sizeof(UdpScan) == sizeof(fpnn_aes_udp_scan) && sizeof(UdpPkg) == sizeof(fpnn_aes_udp_pkg) &&
+                  sizeof(UdpSection) == sizeof(fpnn_aes_udp_section) && sizeof(UdpScan) == 8 && sizeof(UdpPkg) == 16 &&
+                  sizeof(UdpSection) == 16,
+              "the walk tables are the public structs");
+static_assert(UDP_F_WALK_ONLY == FPNN_AES_UDP_F_WALK_ONLY && UDP_F_PLAIN == FPNN_AES_UDP_F_PLAIN &&
+                  UDP_SHORT == FPNN_AES_UDP_SHORT && UDP_VERSION == FPNN_AES_UDP_VERSION && UDP_TYPE == FPNN_AES_UDP_TYPE &&
+                  UDP_ACKS == FPNN_AES_UDP_ACKS && UDP_CLOSE == FPNN_AES_UDP_CLOSE && UDP_FULL == FPNN_AES_UDP_FULL &&
+                  UDP_LONG == FPNN_AES_UDP_LONG,
+              "the plan's and the kernels' values are the public ones");
+
+// The receive calls: recv = [datagram key slots (k_udp_expand over no sections), package decrypt]
+// unless PLAIN, the walk, and unless WALK_ONLY [k_udp_take over every package, the *_frames_at
+// decrypt of its segments]; recv_take = the bracketed data step alone over the take lists.  The
+// scratch and its layout are run_udp_decrypt_calls', with max_sections segments per datagram or
+// taken package in place of the caller's sections.
+int run_udp_recv_calls(fpnn_aes_engine *e, const fpnn_aes_batch *b, const fpnn_aes_udp_data *u, bool take,
+                       uint32_t flags, uint32_t max_pkgs, uint32_t max_sections, const fpnn_aes_udp_scan *scan,
+                       const fpnn_aes_udp_pkg *pkgs, const fpnn_aes_udp_section *sections, const uint32_t *first_take,
+                       const uint32_t *take_list, uint32_t ntake) {
+    if (int rc = check_batch(e, b)) return rc;
+    UdpRecvArgs a = {};
+    a.udp = udp_args(e, b, u);
+    a.take = take;
+    a.flags = flags;
+    a.in_place = b->in == b->out && !b->out_off;
+    a.count = b->count;
+    a.max_pkgs = max_pkgs;
+    a.max_sections = max_sections;
+    a.ntake = ntake;
+    a.scan = (uintptr_t)scan;
+    a.pkgs = (uintptr_t)pkgs;
+    a.sections = (uintptr_t)sections;
+    a.first_take = (uintptr_t)first_take;
+    a.take_list = (uintptr_t)take_list;
+    int rc = udp_recv_check_args(a);
+    if (rc) return rc;
+    if (!u->nconn || !b->count || (take && !ntake)) return FPNN_AES_OK;
+    DeviceGuard g(e->device);
+    const UdpRecvRoute r = udp_recv_route(dispatch_shape(e), batch_shape(b), udp_shape(b, u), take, flags, max_sections, ntake);
+    if (!r.ok) return FPNN_AES_ERR_KEYLEN;
+    if ((rc = scratch_ensure(e, r.need))) return rc;
+    const uint64_t ndg = r.package ? b->count : 0;
+    uint32_t *const dg_slot = e->udp_u32.p, *const sec_n = dg_slot + ndg, *const conn_sec = sec_n + r.nseg;
+    const UdpTable t = udp_table(e, u);
+    const UdpRecvTable rt{const_cast<UdpScan *>(reinterpret_cast<const UdpScan *>(scan)),
+                          const_cast<UdpPkg *>(reinterpret_cast<const UdpPkg *>(pkgs)),
+                          const_cast<UdpSection *>(reinterpret_cast<const UdpSection *>(sections)),
+                          max_pkgs, max_sections, take ? first_take : nullptr, take ? take_list : nullptr,
+                          take ? ntake : 0u, 0u};
+    const FrameTable f{u->first_dgram, u->nconn, u->slot_bound, e->d_fault, u->conn_slot, nullptr};
+    if (r.package) {
+        {
+            const BatchScope batch_scope(e);
+            const KBatch k = make_kbatch(e, b, u->iv_state, u->pos_state);
+            HIP_TRY(launch_udp_expand(k, t, dg_slot, e->udp_off.p, sec_n, conn_sec, e->num_cus, e->stream));
+            batch_queued(e);
+        }
+        fpnn_aes_batch pb = *b;  // the datagrams, each under its connection's slot
+        pb.key_slot = dg_slot;
+        if ((rc = run_decrypt(e, &pb, nullptr, nullptr, false))) return rc;
+    }
+    if (!take) {  // (the walk reads the datagrams where the package layer left them: in `out`)
+        const BatchScope batch_scope(e);
+        KBatch k = make_kbatch(e, b, u->iv_state, u->pos_state);
+        if ((rc = audit_begin(e, b, u->iv_state, u->pos_state, k, &f, &t, u->data_keys, &rt))) return rc;
+        HIP_TRY(launch_udp_walk(k, rt, e->num_cus, e->stream));
+        batch_queued(e);
+        if ((rc = audit_end(e, FPNN_AES_OK))) return rc;
+    }
+    if (!r.data) return FPNN_AES_OK;
+    {
+        const BatchScope batch_scope(e);
+        KBatch k = make_kbatch(e, b, u->iv_state, u->pos_state);
+        if ((rc = audit_begin(e, b, u->iv_state, u->pos_state, k, &f, &t, u->data_keys, &rt))) return rc;
+        HIP_TRY(launch_udp_take(k, t, rt, e->udp_off.p, sec_n, conn_sec, e->num_cus, e->stream));
+        batch_queued(e);
+        if ((rc = audit_end(e, FPNN_AES_OK))) return rc;
+    }
+    fpnn_aes_batch sb;  // the segments: pieces of `out`, in place
+    memset(&sb, 0, sizeof sb);
+    sb.in = sb.out = b->out;
+    sb.count = (uint32_t)r.nseg;
     sb.in_off = e->udp_off.p;
     sb.len = sec_n;
     sb.keys = u->data_keys;
@@ -1315,6 +1418,21 @@ int fpnn_aes_udp_encrypt(fpnn_aes_engine *e, const fpnn_aes_batch *b, const fpnn
 
 int fpnn_aes_udp_decrypt(fpnn_aes_engine *e, const fpnn_aes_batch *b, const fpnn_aes_udp_data *u) {
     return audit_end(e, run_udp_decrypt_calls(e, b, u));
+}
+
+int fpnn_aes_udp_recv(fpnn_aes_engine *e, const fpnn_aes_batch *b, const fpnn_aes_udp_data *u, uint32_t flags,
+                      uint32_t max_pkgs, uint32_t max_sections, fpnn_aes_udp_scan *scan, fpnn_aes_udp_pkg *pkgs,
+                      fpnn_aes_udp_section *sections) {
+    return audit_end(e, run_udp_recv_calls(e, b, u, false, flags, max_pkgs, max_sections, scan, pkgs, sections, nullptr,
+                                           nullptr, 0));
+}
+
+int fpnn_aes_udp_recv_take(fpnn_aes_engine *e, const fpnn_aes_batch *b, const fpnn_aes_udp_data *u, uint32_t max_pkgs,
+                           uint32_t max_sections, const fpnn_aes_udp_scan *scan, const fpnn_aes_udp_pkg *pkgs,
+                           const fpnn_aes_udp_section *sections, const uint32_t *first_take, const uint32_t *take,
+                           uint32_t ntake) {
+    return audit_end(e, run_udp_recv_calls(e, b, u, true, 0, max_pkgs, max_sections, scan, pkgs, sections, first_take,
+                                           take, ntake));
 }
 
 // ---- receive side: wire framing on the device ------------------------------------

@@ -12,29 +12,11 @@
 //         key slot, every section as a segment of `out`, every connection's section range --
 //         and the engine queues the package decrypt and the *_frames_at decrypt behind it
 #include "coop.hpp"
+#include "udp_ranges.hpp"
 
 namespace fpnn_aes {
 
 namespace {
-
-// Entries [r0, r1) of a range table (first_dgram over the datagrams, first_section over the
-// sections): item j of `items` owns [tab[j], tab[j + 1]) of `total`.  The contract is
-// first_frame's (k_stream_frames.hip, stream_range): non-decreasing from 0 to total; what is
-// read is clamped into [0, total], a table that breaks the contract is reported.
-__device__ __forceinline__ void table_range(const KBatch &b, AuditBuf buf, const uint32_t *tab, uint32_t j,
-                                            uint32_t items, uint32_t total, uint32_t *fault, uint32_t &r0,
-                                            uint32_t &r1) {
-    if (!tab) {  // (first_section of a call without sections)
-        r0 = r1 = 0u;
-        return;
-    }
-    const uint32_t t0 = *FA_AT(b, buf, tab + j, 4);
-    const uint32_t t1 = *FA_AT(b, buf, tab + j + 1, 4);
-    const bool bad = t1 < t0 || t1 > total || (j == 0 && t0 != 0u) || (j + 1 == items && t1 != total);
-    r0 = min(t0, total);
-    r1 = max(min(t1, total), r0);
-    if (bad && fault) __hip_atomic_store(fault, kFaultFrameTable, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
 
 // Section s of a datagram of `len` bytes whose earlier sections end at prev_end: its bytes
 // [lo, hi) inside the datagram.  Sections ascend, do not overlap and lie inside the datagram;
@@ -277,18 +259,6 @@ __global__ __launch_bounds__(kThreads, 4) __attribute__((amdgpu_waves_per_eu(4, 
 //   sec_abs[s]   section s as a segment of `out`: its datagram's offset + sec_off[s], and
 //   sec_n[s]     its length, both clamped into the datagram (length 0 when no datagram owns it)
 //   conn_sec[j]  connection j's sections start at first_section[first_dgram[j]]; nconn + 1 entries
-__device__ __forceinline__ uint32_t owner_of(const KBatch &b, AuditBuf buf, const uint32_t *tab, uint32_t items,
-                                             uint32_t x) {
-    // the last j in [0, items) with tab[j] <= x (0 when there is none)
-    uint32_t lo = 0, hi = items;
-    while (hi - lo > 1u) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (*FA_AT(b, buf, tab + mid, 4) <= x) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
-
 __global__ __launch_bounds__(256) void k_udp_expand(KBatch b, UdpTable u, uint32_t *__restrict__ dg_slot,
                                                     uint64_t *__restrict__ sec_abs, uint32_t *__restrict__ sec_n,
                                                     uint32_t *__restrict__ conn_sec) {

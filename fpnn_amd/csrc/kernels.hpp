@@ -205,6 +205,47 @@ hipError_t launch_udp_encrypt(const KBatch &b, const UdpTable &u, int nr_data, i
 // every connection's section range).
 hipError_t launch_udp_expand(const KBatch &b, const UdpTable &u, uint32_t *dg_slot, uint64_t *sec_abs, uint32_t *sec_n,
                              uint32_t *conn_sec, int num_cus, hipStream_t st);
+// UDP v2 receive (k_udp_recv.hip; fpnn_aes_udp_recv / _recv_take).  The three walk tables, the
+// device's mirrors of fpnn_aes_udp_scan / _pkg / _section (engine.hip asserts the sizes):
+// datagram i's rows start at i * max_pkgs and i * max_sections.
+struct UdpScan {
+    uint16_t pkgs, sections;
+    uint8_t version, status;
+    uint16_t reserved;
+};
+struct UdpPkg {
+    uint32_t seq;
+    uint8_t type, flag, sign, status;
+    uint16_t off, len;
+    uint16_t first_section, nsections;
+};
+struct UdpSection {
+    uint8_t type, flag;
+    uint16_t pkg;
+    uint16_t off, len;
+    uint16_t package_id, reserved;
+    uint32_t seg_index;
+};
+enum : uint8_t { UDP_OK = 0, UDP_SHORT = 1, UDP_VERSION = 2, UDP_TYPE = 3, UDP_ACKS = 4, UDP_CLOSE = 5, UDP_FULL = 6,
+                 UDP_LONG = 7 };
+struct UdpRecvTable {
+    UdpScan *scan;
+    UdpPkg *pkgs;
+    UdpSection *sections;
+    uint32_t max_pkgs, max_sections;
+    const uint32_t *first_take, *take;  // recv_take: the packages to decrypt (null: all, in array order)
+    uint32_t ntake, pad;
+};
+// k_udp_walk: one lane per datagram reads its package-plaintext in b.out and writes its scan
+// entry and its package and section rows.
+hipError_t launch_udp_walk(const KBatch &b, const UdpRecvTable &r, int num_cus, hipStream_t st);
+// k_udp_take: the data layer's descriptors for the slot-addressed *_frames decrypt, a fixed
+// max_sections segments per datagram (all packages) or per taken package: sec_abs / sec_n
+// (nseg = items * max_sections entries: a section to decrypt as a segment of b.out, else length
+// 0) and conn_sec (nconn + 1: connection j's segments).  What is read from the caller's tables
+// is clamped and a breach reported (kFaultFrameTable).
+hipError_t launch_udp_take(const KBatch &b, const UdpTable &u, const UdpRecvTable &r, uint64_t *sec_abs,
+                           uint32_t *sec_n, uint32_t *conn_sec, int num_cus, hipStream_t st);
 // K2h (k_hybrid.hip): ragged batches with more chains than quads.  Chains of perm[]
 // in length buckets <= long_bucket run on quads (K2c's cipher), the rest one per lane
 // (K2's); quad_waves waves per workgroup start on the long ones.  ctr: the 2 ticket

@@ -119,6 +119,11 @@ inline ScratchNeed need_ecdh_accept(uint64_t count, uint64_t keylen) {
 // derived descriptors (k_udp.hip, k_udp_expand), the package decrypt of the datagrams on its route
 // (pkg: decrypt_route's need) and the slot-addressed *_frames decrypt of the sections, whose
 // descriptor arrays are the derived ones.  fpnn_aes_udp_encrypt (K2u) needs no scratch.
+// fpnn_aes_udp_recv / _recv_take (k_udp_recv.hip) are the same composition with the sections found
+// on the device: `sections` is then max_sections per datagram (or per taken package) whatever the
+// datagrams hold, 0 under WALK_ONLY; `dgrams` the datagrams the package decrypt runs over (0: PLAIN,
+// or recv_take).  The same buffers in the same layout, so reserve's promise covers those calls
+// when max_segments >= max(dgrams, segments, conns).
 inline ScratchNeed need_udp_decrypt(const ScratchShape &s, const ScratchNeed &pkg, uint64_t dgrams, uint64_t sections,
                                     uint64_t conns) {
     ScratchNeed r = pkg;

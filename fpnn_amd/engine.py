@@ -538,6 +538,77 @@ class Engine:
         self._udp(lib.fpnn_aes_udp_decrypt, "udp_decrypt", inp, out, count, keys, data_keys, nconn, first_dgram,
                   conn_slot, slot_bound, nsections, first_section, sec_off, sec_len, iv_state, pos_state, kw)
 
+    # UDP v2 receive (fpnn_aes_udp_recv / _recv_take): the device package-decrypts the datagrams,
+    # walks their packages and components, and data-decrypts the DATA sections of the packages
+    # taken.  The walk tables are int32 tensors whose rows are the header's structs: scan
+    # [count, 2], pkgs [count * max_pkgs, 4], sections [count * max_sections, 4]
+    # (numpy: .view(udp_scan_dtype) etc.).
+    def _udp_data(self, data_keys, nconn, first_dgram, conn_slot, slot_bound, iv_state, pos_state):
+        for name, t, n in (("first_dgram", first_dgram, nconn + 1), ("conn_slot", conn_slot, nconn)):
+            if t is not None:
+                if t.dtype not in (torch.int32, torch.uint32):
+                    raise TypeError(f"{name}: dtype {t.dtype}, expected {torch.int32}")
+                if t.numel() < n:
+                    raise ValueError(f"{name}: {t.numel()} entries, {n} needed")
+        u = UdpData()
+        u.data_keys = data_keys.handle.value if data_keys is not None else None
+        u.nconn = nconn
+        u.slot_bound = slot_bound
+        for name, t in (("first_dgram", first_dgram), ("conn_slot", conn_slot), ("iv_state", iv_state),
+                        ("pos_state", pos_state)):
+            setattr(u, name, _ptr(t).value if t is not None else None)
+        return u
+
+    @staticmethod
+    def _udp_tables(count, max_pkgs, max_sections, scan, pkgs, sections, device=None):
+        """The three walk tables, checked; device: make the ones not given (udp_recv's outputs)."""
+        made = []
+        for name, t, rows, words in (("scan", scan, count, 2), ("pkgs", pkgs, count * max_pkgs, 4),
+                                     ("sections", sections, count * max_sections, 4)):
+            if t is None:
+                if device is None:
+                    raise ValueError(f"{name}: the table of the udp_recv call is needed")
+                t = torch.zeros((max(rows, 1), words), dtype=torch.int32, device=device)
+            if t.dtype != torch.int32 or t.numel() < rows * words:
+                raise ValueError(f"{name}: int32 tensor of {rows * words} words needed")
+            made.append(t)
+        return made
+
+    def udp_recv(self, inp, out, count, keys: "KeySet", data_keys: Optional["KeySet"], nconn: int,
+                 first_dgram: torch.Tensor, conn_slot: torch.Tensor, slot_bound: int, iv_state: torch.Tensor,
+                 pos_state: torch.Tensor, max_pkgs: int, max_sections: int, flags: int = 0, scan=None, pkgs=None,
+                 sections=None, **kw):
+        """-> (scan, pkgs, sections): the device tables (given ones are filled and returned)."""
+        d = self._desc(inp, out, count, keys, **kw)
+        u = self._udp_data(data_keys, nconn, first_dgram, conn_slot, slot_bound, iv_state, pos_state)
+        scan, pkgs, sections = self._udp_tables(count, max_pkgs, max_sections, scan, pkgs, sections, out.device)
+        check(lib.fpnn_aes_udp_recv(self._h, C.byref(d), C.byref(u), flags, max_pkgs, max_sections, _ptr(scan),
+                                    _ptr(pkgs), _ptr(sections)), "udp_recv")
+        return scan, pkgs, sections
+
+    def udp_recv_take(self, inp, out, count, keys: "KeySet", data_keys: "KeySet", nconn: int,
+                      first_dgram: torch.Tensor, conn_slot: torch.Tensor, slot_bound: int, iv_state: torch.Tensor,
+                      pos_state: torch.Tensor, max_pkgs: int, max_sections: int, scan: torch.Tensor,
+                      pkgs: torch.Tensor, sections: torch.Tensor, first_take: torch.Tensor, take: torch.Tensor,
+                      ntake: int, **kw):
+        d = self._desc(inp, out, count, keys, **kw)
+        u = self._udp_data(data_keys, nconn, first_dgram, conn_slot, slot_bound, iv_state, pos_state)
+        scan, pkgs, sections = self._udp_tables(count, max_pkgs, max_sections, scan, pkgs, sections)
+        for name, t, n in (("first_take", first_take, nconn + 1), ("take", take, ntake)):
+            if t is not None and (t.dtype not in (torch.int32, torch.uint32) or t.numel() < n):
+                raise ValueError(f"{name}: int32 tensor of {n} entries needed")
+        check(lib.fpnn_aes_udp_recv_take(self._h, C.byref(d), C.byref(u), max_pkgs, max_sections, _ptr(scan), _ptr(pkgs),
+                                         _ptr(sections), _ptr(first_take), _ptr(take), ntake), "udp_recv_take")
+
+
+# numpy views of the walk tables' rows (Engine.udp_recv): table.cpu().numpy().view(dtype)
+udp_scan_dtype = np.dtype([("pkgs", "<u2"), ("sections", "<u2"), ("version", "u1"), ("status", "u1"),
+                           ("reserved", "<u2")])
+udp_pkg_dtype = np.dtype([("seq", "<u4"), ("type", "u1"), ("flag", "u1"), ("sign", "u1"), ("status", "u1"),
+                          ("off", "<u2"), ("len", "<u2"), ("first_section", "<u2"), ("nsections", "<u2")])
+udp_section_dtype = np.dtype([("type", "u1"), ("flag", "u1"), ("pkg", "<u2"), ("off", "<u2"), ("len", "<u2"),
+                              ("package_id", "<u2"), ("reserved", "<u2"), ("seg_index", "<u4")])
+
 
 def host_register(buf: np.ndarray):
     """fpnn_aes_host_register over a numpy buffer's memory (e.g. a socket-buffer arena):

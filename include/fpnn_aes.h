@@ -391,6 +391,147 @@ typedef struct {
 int fpnn_aes_udp_encrypt(fpnn_aes_engine *e, const fpnn_aes_batch *b, const fpnn_aes_udp_data *u);
 int fpnn_aes_udp_decrypt(fpnn_aes_engine *e, const fpnn_aes_batch *b, const fpnn_aes_udp_data *u);
 
+/* ---- UDP v2 receive: walk the packages on the device, then decrypt (§8f row 2) -------- */
+/* fpnn_aes_udp_decrypt needs the data sections' places, which a receiver learns only from the
+ * package-decrypted datagram.  These two calls package-decrypt the datagrams, walk UDP v2's
+ * package and component structure as ARQParser does (core/UDP.v2/UDPParser.v2.cpp: parse
+ * :59-122, processAssembledPackage :124-159, processPackage :313-346, parseCOMBINED :528-587,
+ * the header arithmetic of parseDATA :672-742, parseACKS :840-870, parseUNA :872-892), report
+ * it in three small device tables, and data-decrypt the DATA sections of the packages the
+ * host's ARQ accepts, continuing each connection's data chain.
+ *
+ * b and u are fpnn_aes_udp_decrypt's (b->key_slot NULL; conn_slot names the package key, the
+ * data key and the state entry), except that the sections are outputs: u->first_section,
+ * u->sec_off and u->sec_len must be NULL and u->nsections 0.  u->data_keys may be NULL only
+ * with FPNN_AES_UDP_F_WALK_ONLY.  scan has b->count entries, pkgs b->count * max_pkgs,
+ * sections b->count * max_sections (device arrays; both products must fit 32 bits); datagram
+ * i's rows start at i * max_pkgs and i * max_sections; entries past the used counts are not
+ * written.  b->out holds the package-decrypted bytes of every datagram, whatever its status.
+ *
+ * The walk, per datagram (it reads the datagram's own bytes only, whatever they hold):
+ *   len < 8: FPNN_AES_UDP_SHORT, no package.  len > 65535: FPNN_AES_UDP_LONG, no package (no
+ *   UDP datagram is; the tables' offsets are 16 bits).  Version byte > 2: FPNN_AES_UDP_VERSION,
+ *   no package; otherwise the version is recorded.  Type 0x81 (ARQ_ASSEMBLED): from offset 2,
+ *   included packages [be16 length][type flag sign seq4 payload], each one a package row with
+ *   the reference's _buffer / _bufferLength (:133-134): off = the length field's second byte,
+ *   len = length + 1.  Any other type: one package over the whole datagram (off 0).
+ *   Package, by type: COMBINED (0x80) needs len >= 16; its components start at offset 8, each
+ *   [type flag be16 bytes] with offset + 4 + bytes <= len, of type DATA, ACKS, UNA, FORCESYNC
+ *   or CLOSE.  A whole package may also be a HEARTBEAT.  ECDH (these calls serve encrypted
+ *   connections, and the reference refuses ECDH on one, :928-933) and every other type:
+ *   FPNN_AES_UDP_TYPE.  ACKS whose bytes are no multiple of 4: FPNN_AES_UDP_ACKS.  A whole-
+ *   package UNA needs len == 12.  A UNA component inside COMBINED is accepted as the reference
+ *   accepts it, whenever the 4 bytes after its header lie inside the package (:888 reads them
+ *   whatever `bytes` says): its section's len is the component's `bytes`, which may be less
+ *   than 4 -- the UNA value is then the 4 bytes at off all the same, running into the next
+ *   component; a host ARQ reads 4 bytes at off, not len bytes.  CLOSE is recorded as a section and ends its PACKAGE with
+ *   status FPNN_AES_UDP_CLOSE, which the ARQ accepts (:336-340, :567-571): the datagram's walk
+ *   goes on with the next included package and the datagram's status stays OK.
+ *   DATA: flag & 0x0c selects no segment header (0) or packageId (be16) + a 1- (0x04), 2-
+ *   (0x08) or 4-byte (0x0c) big-endian index; off / len are the bytes after that header.
+ *   Wherever the reference would read a byte outside the package or wrap an unsigned length
+ *   the status is FPNN_AES_UDP_SHORT at that point: a component header or a combined UNA's 4
+ *   bytes that cross the package's end, a segment header longer than its section (a cancelled
+ *   one included: the reference reads only its packageId, but no sender writes less than the
+ *   whole header), an included package of length < 7 or one that runs past the datagram, a
+ *   1-byte remainder after the last included package.  An included package that is SHORT in
+ *   one of these last three ways gets no row (its header is not all there): the datagram's
+ *   status carries it.
+ *   A rejected package keeps the sections recorded before the point of rejection (the
+ *   reference has processed them by then), carries the reason in its status, and ends the
+ *   datagram's walk (:150-151, :580-581) with the same status for the datagram.  When a row
+ *   has no room for the next entry the status (package and datagram) is FPNN_AES_UDP_FULL;
+ *   what fits is recorded.
+ *
+ * Data decrypt: a section is decrypted when it is DATA without ARQ_Discardable (0x01) and
+ * without ARQ_CancelledPackage (0x80) (:695-703, :714, :769-775, :823-829), in place in b->out,
+ * continuing the slot's (iv_state, pos_state), which is updated in place.
+ *   fpnn_aes_udp_recv without WALK_ONLY takes every package of every datagram in array order:
+ *   the single-call form for a caller that has established processing order already.
+ *   fpnn_aes_udp_recv_take takes connection j's packages take[first_take[j] .. first_take[j+1])
+ *   in that order, each a global package index i * max_pkgs + k of one of the connection's own
+ *   datagrams (first_take: device, nconn + 1 entries, first_frame's contract over ntake; take:
+ *   device, ntake entries).  It follows a WALK_ONLY call once the host's ARQ has read pkgs[]
+ *   (b, u, max_pkgs, max_sections and the tables as in that call), or a PLAIN | WALK_ONLY call
+ *   for datagrams that came back from the disordered cache.
+ * Connections with nothing to decrypt, slots not named, and everything under WALK_ONLY keep
+ * every bit of their state.
+ *
+ * Why the split is exact: once data encryption is on the reference parses in order
+ * (:978): reliable packages are processed strictly by sequence and out-of-order ones are
+ * cached as package-plaintext and processed later (:225-250).  A walk that needs no data
+ * layer, then "decrypt these packages' sections in this order", is what it does.
+ *
+ * Limits.  ARQ decisions stay on the host: sequence order, the ARQ checksum
+ * (UDPCommon.v2.cpp:6-36), the disordered cache, segment assembly; so does the ECDH-copy filter
+ * (:76-89), which the caller applies before the call.  The device does not decode payloads:
+ * the reference stops a COMBINED walk when decodeBuffer rejects an unsegmented payload
+ * (:699-703) and skips the decrypt on assembly-state rejections (:744-818) -- its chain is out
+ * of step with the sender's from there on anyway; the device decrypts every qualifying
+ * section of a taken package.
+ *
+ * FPNN_AES_ERR_ARG: what fpnn_aes_udp_decrypt reports; unknown flags; PLAIN with b->in !=
+ * b->out or b->out_off; non-NULL section inputs or nsections != 0 in u; data_keys NULL without
+ * WALK_ONLY (recv) or at all (recv_take); max_pkgs == 0 or max_sections == 0, or a product
+ * with b->count (recv_take: max_sections * ntake) above 32 bits; with b->count != 0, a NULL or
+ * misaligned table (scan: 2 bytes; pkgs, sections: 4); with ntake != 0, NULL or misaligned
+ * first_take or take.  FPNN_AES_ERR_KEYLEN for a 24-byte table.  conn_slot[j] >= slot_bound is
+ * handled as by fpnn_aes_udp_decrypt.  Every value read from the caller's device tables
+ * (first_dgram, first_take, take, and scan / pkgs / sections passed back in) is clamped
+ * before it addresses memory; a breach (a table not monotone, a take entry out of range, one
+ * that names no walked package or another connection's datagram, a package or section row
+ * that leaves its datagram) decrypts nothing for that entry, leaves all other connections
+ * exact, and makes the next fpnn_aes_engine_sync return FPNN_AES_ERR_DEVICE once.  Naming one
+ * package twice is the caller's error: wrong plaintext, inside the datagrams' own bytes.
+ *
+ * nconn == 0 or b->count == 0 queues nothing (recv_take: also ntake == 0).  Both calls are
+ * queued on the engine's stream with no host wait.  The data layer runs as max_sections
+ * segments per datagram (recv) or per taken package (recv_take), empty where there is no
+ * section to decrypt; after fpnn_aes_engine_reserve(max_segments, max_blocks) with
+ * max_segments >= max(b->count, nconn, b->count * max_sections) for recv and
+ * max_segments >= max(nconn, ntake * max_sections) for recv_take (max_blocks as for
+ * fpnn_aes_udp_decrypt) they allocate nothing. */
+#define FPNN_AES_UDP_F_WALK_ONLY 0x1u  /* package-decrypt and walk; no data decrypt, state untouched */
+#define FPNN_AES_UDP_F_PLAIN     0x2u  /* b->out already holds package-plaintext (b->in == b->out): skip the package layer */
+
+#define FPNN_AES_UDP_OK      0
+#define FPNN_AES_UDP_SHORT   1 /* a length the reference's reads would leave */
+#define FPNN_AES_UDP_VERSION 2 /* version byte above 2 */
+#define FPNN_AES_UDP_TYPE    3 /* a package or component type the parser refuses (ECDH included) */
+#define FPNN_AES_UDP_ACKS    4 /* ACKS bytes no multiple of 4 */
+#define FPNN_AES_UDP_CLOSE   5 /* package only: ended at a CLOSE; accepted */
+#define FPNN_AES_UDP_FULL    6 /* max_pkgs or max_sections reached */
+#define FPNN_AES_UDP_LONG    7 /* datagram only: more than 65535 bytes */
+
+typedef struct {       /* per datagram */
+    uint16_t pkgs, sections;   /* rows used in the two tables */
+    uint8_t  version, status;  /* FPNN_AES_UDP_* of the datagram as a whole */
+    uint16_t reserved;         /* 0 */
+} fpnn_aes_udp_scan;
+
+typedef struct {       /* per package: the datagram itself, or each package included in an ARQ_ASSEMBLED one */
+    uint32_t seq;              /* be32toh of header bytes 4..8 */
+    uint8_t  type, flag, sign, status;
+    uint16_t off, len;         /* the reference's _buffer and _bufferLength for this package, inside the datagram */
+    uint16_t first_section, nsections;   /* into the datagram's row of the section table */
+} fpnn_aes_udp_pkg;
+
+typedef struct {       /* per component walked: DATA, ACKS, UNA, FORCESYNC, CLOSE, HEARTBEAT */
+    uint8_t  type, flag;       /* a whole package's: the package's type and flag */
+    uint16_t pkg;              /* index in the datagram's package row */
+    uint16_t off, len;         /* payload inside the datagram; for segmented DATA, after packageId and index */
+    uint16_t package_id, reserved;       /* segmented DATA: packageId; else 0 */
+    uint32_t seg_index;        /* segmented DATA: the index; else 0 */
+} fpnn_aes_udp_section;
+
+int fpnn_aes_udp_recv(fpnn_aes_engine *e, const fpnn_aes_batch *b, const fpnn_aes_udp_data *u, uint32_t flags,
+                      uint32_t max_pkgs, uint32_t max_sections,
+                      fpnn_aes_udp_scan *scan, fpnn_aes_udp_pkg *pkgs, fpnn_aes_udp_section *sections);
+int fpnn_aes_udp_recv_take(fpnn_aes_engine *e, const fpnn_aes_batch *b, const fpnn_aes_udp_data *u,
+                           uint32_t max_pkgs, uint32_t max_sections, const fpnn_aes_udp_scan *scan,
+                           const fpnn_aes_udp_pkg *pkgs, const fpnn_aes_udp_section *sections,
+                           const uint32_t *first_take, const uint32_t *take, uint32_t ntake);
+
 /* ---- single call from host memory (the per-frame drop-in) --------------------------- */
 /* Exactly rijndael_cfb_encrypt(ctx, encrypt, in, out, len, ivec, p_num)
  * (base/rijndael.c:1171-1201) with host buffers: stages through pinned memory,

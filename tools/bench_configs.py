@@ -17,6 +17,9 @@ for DESIGN.md -- bench.py's single JSON line covers C2 only.
   U2  U1's datagrams with the data layer, 16384 connections x 64 datagrams, section [12, 1472), AES-128
       package + AES-256 data keys: fpnn_aes_udp_* against the same work composed from the older calls
       and against the data chain alone; U2c: 262144 connections x 4 datagrams              (on request)
+  U2r the U2 and U2c datagrams as real wire datagrams (8-byte header, one segmented DATA section with a
+      2-byte index, payload [12, 1472)) through one fpnn_aes_udp_recv call, which finds the sections
+      itself, beside fpnn_aes_udp_decrypt with the sections supplied                        (on request)
 """
 import argparse
 import json
@@ -388,6 +391,78 @@ def main():
         out[uname] = res
         del a, b, tmp, r
         print(json.dumps({uname: res}), flush=True)
+
+    if "U2r" in todo:
+        # The receive side of U2 / U2c: the same datagrams, now real wire datagrams -- version 2,
+        # ARQ_DATA, a 2-byte segment index: [2 1 0x08 sign seq4 packageId2 index2] and 1460 bytes of
+        # payload -- so the device can find the section [12, 1472) by walking them.  One
+        # fpnn_aes_udp_recv call (package decrypt, k_udp_walk, k_udp_take, data decrypt over one
+        # segment per datagram) beside fpnn_aes_udp_decrypt told where the sections lie: the cipher
+        # work is identical, the difference is the walk and the descriptor kernels.  Wall time per
+        # call, GiB/s of datagram bytes; walk_only: package decrypt and walk alone.
+        c = W.U1
+        P, L = c["packets"], c["length"]
+        i32 = lambda t: t.to(torch.int32).contiguous()  # noqa: E731
+        ar = lambda n: torch.arange(n, dtype=torch.int64, device="cuda")  # noqa: E731
+        a = torch.empty(P * L, dtype=torch.uint8, device="cuda")
+        eng.fill_synthetic(a, c["payload_seed"])
+        hdr = a.view(P, L)[:, :12]
+        hdr[:, 0], hdr[:, 1], hdr[:, 2] = 2, 0x01, 0x08
+        for k in range(4):  # seq, big endian; packageId and index keep the synthetic bytes
+            hdr[:, 4 + k] = ((ar(P) >> (8 * (3 - k))) & 0xFF).to(torch.uint8)
+        b, r = torch.empty_like(a), torch.empty_like(a)
+        first_section = i32(ar(P + 1))
+        sec_off = torch.full((P,), 12, dtype=torch.int32, device="cuda")
+        sec_len = torch.full((P,), L - 12, dtype=torch.int32, device="cuda")
+        scan = torch.zeros((P, 2), dtype=torch.int32, device="cuda")
+        pkgs, secs = (torch.zeros((P, 4), dtype=torch.int32, device="cuda") for _ in range(2))
+        res = {}
+        for shape, NC in (("U2", 16384), ("U2c", 262144)):
+            DG = P // NC
+            pk, piv = W.many_keys(dict(c, connections=NC))
+            dk, div = W.many_keys(dict(c, connections=NC, keylen=32, key_seed=c["key_seed"] + 1))
+            ksp = fpnn_amd.KeySet(eng, pk.tobytes(), 16, piv.tobytes())
+            ksd = fpnn_amd.KeySet(eng, dk.tobytes(), 32, div.tobytes())
+            first_dgram, conn_slot = i32(ar(NC + 1) * DG), i32(ar(NC))
+            iv0 = torch.from_numpy(div.copy()).cuda()
+            iv_s, pos_s = iv0.clone(), torch.zeros(NC, dtype=torch.int32, device="cuda")
+
+            def reset():
+                iv_s.copy_(iv0)
+                pos_s.zero_()
+
+            def supplied(fn, src, dst):
+                fn(src, dst, P, ksp, ksd, NC, first_dgram, conn_slot, NC, P, first_section, sec_off, sec_len, iv_s, pos_s,
+                   stride=L, uniform_len=L)
+
+            def recv(flags=0):
+                eng.udp_recv(b, r, P, ksp, ksd, NC, first_dgram, conn_slot, NC, iv_s, pos_s, 1, 1, flags=flags, scan=scan,
+                             pkgs=pkgs, sections=secs, stride=L, uniform_len=L)
+
+            # both ways give the plaintext and the same state, before anything is timed
+            reset()
+            supplied(eng.udp_encrypt, a, b)
+            reset()
+            supplied(eng.udp_decrypt, b, r)
+            assert torch.equal(r, a), shape + ": decrypt(encrypt(x)) != x"
+            iv_want, pos_want = iv_s.clone(), pos_s.clone()
+            r.zero_()
+            reset()
+            recv()
+            assert torch.equal(r, a), shape + ": udp_recv's plaintext differs"
+            assert torch.equal(iv_s, iv_want) and torch.equal(pos_s, pos_want), shape + ": udp_recv's state differs"
+            assert bool(torch.all(scan[:, 0] == 0x00010001)) and bool(torch.all(scan[:, 1] == 2)), shape + ": walk"
+            one = {}
+            for name, fn in (("recv", recv), ("decrypt_supplied", lambda: supplied(eng.udp_decrypt, b, r)),
+                             ("walk_only", lambda: recv(1))):
+                w, _, _ = timed(eng, D, fn, args.reps)
+                one[name + "_wall_GiBs"] = gib(P * L, w)
+            one["recv_over_supplied"] = round(one["recv_wall_GiBs"] / one["decrypt_supplied_wall_GiBs"], 3)
+            res[shape] = one
+            del ksp, ksd
+        out["U2r"] = res
+        del a, b, r
+        print(json.dumps({"U2r": res}), flush=True)
 
     for qname in [q for q in ("Q1", "Q1g", "Q1s", "Q1h") if q in todo]:
         # FPNN's typical quest frames (145 B: core/test/tcp-test/asyncStressClient.cpp:13-29)
